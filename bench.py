@@ -6,7 +6,7 @@ One STEP = one scheduler step = 2 DiT forwards (cond + uncond, cfg 5) + fused un
 over synthetic 93x480x832 latents (16x24x60x104, S = 37,440 tokens), random-init weights of the
 named architecture, non-zero guidance-buffer tokens, inputs resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 1.3b|14b]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 1.3b|14b] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -44,7 +44,7 @@ from infinicube_amd.videogen.config import GRID_480P, TokenGrid, dit_forward_flo
 from infinicube_amd.videogen.dit import WanDiT  # noqa: E402
 from infinicube_amd.videogen.ops import HipOps  # noqa: E402
 from infinicube_amd.videogen.scheduler import FlowMatchScheduler  # noqa: E402
-from infinicube_amd.videogen.seqpar import BranchExchange, ParallelLayout, autotune_kv_exchange  # noqa: E402
+from infinicube_amd.videogen.seqpar import BranchExchange, ParallelLayout, autotune_kv_exchange, gather_latent  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 XGMI_LINKS, XGMI_LINK_GBS = 7, 153.0     # per GPU, point to point (task statement / MI355X guide)
@@ -201,7 +201,28 @@ def parse_args(argv=None):
                          "off unless asked for (tools/e2e_wallclock.py is the same measurement on its own)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the full latent the last timed step left (for N>1 the ranks' token "
+                         "shards gathered, as the pipeline does after its loop) as DIR/latent.npy in float32, so that two builds "
+                         "can be compared output for output on the same seeded inputs")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  One whose share of the 64 MB budget is too small
+    for it is written as a fixed sample of its flattened elements (seeded index set, the same in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_LIMIT_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32)
+        if a.numel() > cap:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a.numpy())
 
 
 def error_record(args, world, message, failed=None, phase=None):
@@ -605,6 +626,11 @@ def run_rank(args, world, rank, phase, stdout_fd):
     elapsed = time.perf_counter() - t0
     record["on"] = False
     phase("report")
+    if args.dump_outputs:      # before the untimed issue-time step below moves the latent on
+        # each rank stepped only its own tokens: every rank takes part in the gather, rank 0 writes the full latent
+        full = gather_latent(latent, plan, grid, group=layout.sp_group)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"latent": full})
     abi_calls = native.N_CALLS[0] - calls0
     kv_waits = list(model.kv_gather.timing or []) if model.kv_gather is not None else []
     n_coll = model.kv_gather.n_collectives if model.kv_gather is not None else 0
@@ -749,7 +775,10 @@ def run_rank(args, world, rank, phase, stdout_fd):
             out["e2e"] = e2e_mod.run_e2e(args.model, args.e2e, args.gemm_dtype, str(device), log=lambda m: print(f"[e2e] {m}", file=sys.stderr, flush=True))
             out["e2e"]["loop_only_50_steps_s"] = out["config"]["wallclock_50_steps_s"]
         if world == 1 and not args.no_cpu_baseline:
-            threads = args.cpu_threads or min(os.cpu_count() or 1, 32)  # >32 threads oversubscribes these GEMM sizes
+            # >32 threads oversubscribes these GEMM sizes; OMP_NUM_THREADS, where set, is the share of the host this run may use
+            # (its first field: the variable may list one count per nesting level, "16,2")
+            omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+            threads = args.cpu_threads or min(int(omp) if omp.isdigit() and int(omp) > 0 else (os.cpu_count() or 1), 32)
             out["cpu_baseline"] = cpu_baseline(cfg, grid, threads)
         if not guard.write_result(out):      # under a supervisor ITS rank 0 prints the line (with the attempt history)
             emit(out, stdout_fd)

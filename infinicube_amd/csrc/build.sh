@@ -10,7 +10,8 @@ out="${ICV_LIB_OUT:-$here/libicvideo.so}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I"$root/include" -I"$here" -Wno-unused-result)
 objs=()
-pids=()
+running=0
+max_jobs="${MAX_JOBS:-16}"       # concurrent hipcc processes: one per CPU this build may use, not one per source
 mkdir -p "$here/build"
 srcs=(api elementwise gemm gemm256 gemm256p gemm_fp8 fp8 attention attn2 attn7 attn7p attn8 buffers voxels vae_ops dit_forward comm ipc conv)
 tag=""
@@ -25,12 +26,13 @@ for src in "${srcs[@]}"; do
     extra=()
     # buffers.hip produces BYTE outputs that must equal the reference's: no fused multiply-add contraction there
     [[ "$src" == buffers || "$src" == voxels ]] && extra=(-ffp-contract=off)
+    if (( running >= max_jobs )); then wait -n; running=$((running - 1)); fi   # a failed compile ends the script here (set -e)
     "$HIPCC" "${FLAGS[@]}" "${extra[@]}" "$@" -c "$here/$src.hip" -o "$obj" &
-    pids+=($!)
+    running=$((running + 1))
   fi
   objs+=("$obj")
 done
-for p in "${pids[@]:-}"; do [[ -n "$p" ]] && wait "$p"; done
+while (( running > 0 )); do wait -n; running=$((running - 1)); done
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -ldl -o "$out"
 python3 -c "import ctypes,sys; ctypes.CDLL(sys.argv[1])" "$out"   # unresolved symbols fail here, not on the GPU box
 echo "built $out"

@@ -50,7 +50,9 @@ def run_ranks(n, out, args, timeout=420, extra_env=None):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    PYTHONPATH=os.pathsep.join([ROOT, HERE, os.environ.get("PYTHONPATH", "")]), OMP_NUM_THREADS="2")
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        env.setdefault("GPU_MAX_HW_QUEUES", "16")      # what every real launcher of ranks sets (the copy-engine transport refuses a process without it)
+        # the value the product's launchers default to; they honour an inherited smaller one (then the copy-engine transport
+        # refuses >= 3 ranks and drops out), so this test overrides what it inherited instead of deferring to it
+        env["GPU_MAX_HW_QUEUES"] = "16"
         env.update(extra_env or {})
         procs.append(subprocess.Popen([sys.executable, WORKER, "--out", out] + [str(x) for x in args], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL))
@@ -372,7 +374,7 @@ def test_copy_engine_transport_one_rank_failing_is_an_error_on_every_rank_not_a_
                    PYTHONPATH=os.pathsep.join([ROOT, HERE, os.environ.get("PYTHONPATH", "")]), OMP_NUM_THREADS="2",
                    ICV_TEST_HOOKS="1", ICV_IPC_INJECT=f"selftest:{bad}")
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        env.setdefault("GPU_MAX_HW_QUEUES", "16")
+        env["GPU_MAX_HW_QUEUES"] = "16"
         procs.append(subprocess.Popen([sys.executable, "-c", IPC_ABORT_WORKER], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                                       stdin=subprocess.DEVNULL))
     t0, outs = time.time(), []
@@ -526,6 +528,34 @@ def test_bench_stdout_is_one_json_line_on_one_gpu(n, launcher):
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_is_the_gathered_latent(tmp_path):
+    """`bench.py --dump-outputs` with N ranks writes the FULL latent: two `sp` ranks sharing the GPU over gloo each step only
+    their own half of the tokens, so what rank 0 dumps must be the gathered latent.  Compared as the change the timed steps made
+    to the seeded noise (a few steps of a 50-step schedule move the latent little): a half left at the noise fails by far."""
+    import numpy as np
+    from infinicube_amd.videogen import synthetic as syn
+    from infinicube_amd.videogen.config import TokenGrid
+    tail = ["--model", "small", "--frames", "9", "--height", "128", "--width", "160", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+
+    def run(n, extra, env_extra):
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        env.update(env_extra)
+        d = tmp_path / f"dump{n}"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n)] + tail + extra + ["--dump-outputs", str(d)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return torch.from_numpy(np.load(d / "latent.npy"))
+
+    noise = syn.make_latent_noise(TokenGrid(9, 128, 160), seed=0)
+    ref = run(1, [], {})
+    got = run(2, ["--parallelism", "sp", "--kv-exchange", "allgather"],
+              dict(ICV_BENCH_SHARE_GPU="1", ICV_DIST_BACKEND="gloo", ICV_GUARD_BUDGETS="autotune=400,warmup=400,timed=400"))
+    assert got.shape == ref.shape == noise.shape and got.dtype == torch.float32
+    _close({"result": got - noise, "info": "2 sp ranks, gathered dump"}, {"result": ref - noise}, "bench --dump-outputs, latent change",
+           rel_bound=5e-2, psnr_bound=30.0)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("inject,plan_prefix,n_failed", [("0:1:groups:raise", "cfg+sp / kv-exchange allgather", 1),
                                                         ("0:3:autotune:hang,1:0:warmup:raise", "sp / kv-exchange allgather", 2)])
 def test_bench_falls_back_and_says_so(inject, plan_prefix, n_failed):
@@ -599,6 +629,8 @@ def _pool_frames(tmp_path, monkeypatch, n, backend, share, factory="gpu_factory"
         return g, np.stack([np.asarray(f) for f in frames])
 
     _, ref = run()
+    # the pool only defaults the variable (an inherited value wins): clear it so the ranks get the pool's default of 16
+    monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
     monkeypatch.setenv("ICV_WORLD", str(n))
     monkeypatch.setenv("ICV_DIST_BACKEND", backend)
     monkeypatch.setenv("ICV_WORKER_FACTORY", f"mgpu_factory:{factory}")
@@ -642,6 +674,8 @@ def test_worker_pool_client_with_hip_already_initialised_four_ranks_copy_engine_
     x = torch.randn(512, 512, device="cuda:0")
     y = (x @ x).sum().item()                                     # the caller's own GPU work, before the generator exists
     assert torch.cuda.is_initialized() and y == y
+    # the pool only defaults the variable (an inherited value wins): clear it so the ranks get the pool's default of 16
+    monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
     env_before = {k: os.environ.get(k) for k in ("GPU_MAX_HW_QUEUES", "NCCL_MAX_NCHANNELS", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     monkeypatch.setenv("ICV_PARALLELISM", "sp")
     monkeypatch.setenv("ICV_WORLD_FALLBACK", "0")                # the forced plan or an error: no silent ladder in this test

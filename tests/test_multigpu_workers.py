@@ -44,6 +44,8 @@ def test_generator_spawns_workers_and_matches_single_process(tmp_path, monkeypat
     path = _checkpoint(tmp_path)
     _, ref1, ref2, out_single, log_single = _run(path, tmp_path, "single.mp4")
     assert os.path.getsize(out_single) > 0
+    # the pool only defaults the variable (an inherited value wins): clear it so the ranks get the pool's default of 16
+    monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
     monkeypatch.setenv("ICV_WORLD", str(world))
     monkeypatch.setenv("ICV_DIST_BACKEND", "gloo")
     monkeypatch.setenv("ICV_WORKER_FACTORY", "mgpu_factory:factory")
