@@ -33,7 +33,9 @@ extern "C" {
  * 4: icv_attention_fwd_pieces (ONE arrival-gated attention launch per layer over K|V pieces), icv_ipc_arrival / _gather_consumed / _configure / _check /
  *    _drain / _probe_copy, icv_probe_copy_path (arrival flags, bounded device-side waits, teardown that does not depend on live peers, copy-engine-or-blit
  *    probe), icv_flag_write; no existing
- *    signature changed. */
+ *    signature changed.
+ * 5: icv_attention_fp8_fwd_pieces_gated (the e4m3 chunk launches gate on their pieces' arrival flags inside the kernel); no existing
+ *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -495,6 +497,15 @@ int icv_ipc_abort(icv_ipc* ipc);
 
 /* ---- dtype plumbing: f32 -> bf16 (round-to-nearest-even), n elements ---------------------- */
 int icv_cast_f32_to_bf16(const float* in, void* out, int64_t n, void* stream);
+
+/* ---- TeaCache step skipping -----------------------------------------------------------------------------
+ * icv_sub_rows_f32: r[i, j] = x[i, j] - r[i, j] in place over [rows, d] f32 (row strides ldx, ldr): the residual store of a
+ * computed forward (x = residual stream after the blocks, r = the patch-GEMM output of the same step).  Plain fp32 subtraction.
+ * icv_rel_l1_steps_f32: table f32 [n, cols] (row stride ldt) of t_mod rows, one per step -> out f32 [n]:
+ * out[i] = mean|t_i - t_{i-1}| / mean|t_{i-1}| for i >= 1, out[0] = 0.  Deterministic (fixed fp64 reduction order, no atomics):
+ * every rank computes the same bits.  Replaces the per-step distance of upstream DiffSynth's TeaCache.check [EXT]. */
+int icv_sub_rows_f32(const float* x, int64_t ldx, float* r, int64_t ldr, int64_t rows, int64_t d, void* stream);
+int icv_rel_l1_steps_f32(const float* table, int64_t n, int64_t cols, int64_t ldt, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -294,6 +294,7 @@ class WanDiT:
         self.t_e = a((1, d), F32)
         self.t_mod = a((1, 6 * d), F32)
         self._t_cached = None
+        self._tc_res = None                # TeaCache residuals, one f32 [n, d] per CFG branch (allocated on first use)
         env = os.environ.get("ICV_GRAPHS")
         if env is not None:
             graphs = env == "1"
@@ -1007,23 +1008,46 @@ class WanDiT:
             self._twin = (twin, torch.cuda.Stream(device=self.ops.device))
         return self._twin
 
+    # ------------------------------------------------------------------------------------
+    # TeaCache (teacache.py).  A computed step leaves R = x_after_blocks - P in the branch's residual, P = the patch
+    # GEMM of this step's latent WITHOUT the step-invariant buffer / i2v tokens; a skipped step is then forward_tokens(latent, ctx, ts,
+    # R, head_out, num_layers=0): patch embed with R added in the GEMM epilogue (= P' + buffer tokens + the blocks' residual), the head.
+    def _tc_residuals(self):
+        if self._tc_res is None:
+            n, d = self.plan.n_tok, self.cfg.dim
+            self._tc_res = (self.ops.alloc((n, d), F32), self.ops.alloc((n, d), F32))
+        return self._tc_res
+
+    def _tc_store(self, patches: torch.Tensor, x: torch.Tensor, r: torch.Tensor):
+        """r = x - (patches @ patch_w.T + patch_b): the residual of a computed forward whose stream ended in ``x``."""
+        self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
+        self.ops.sub_rows(x, r)
+
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
-                branch_exchange=None, round_bf16: bool = False) -> torch.Tensor:
+                branch_exchange=None, round_bf16: bool = False, tea_cache=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
         cond one if it was given ``ctx_cond`` only, the uncond one if ``ctx_uncond`` only — and swaps velocity
         tokens with the rank that runs the other branch on the same token shard.
-        ``round_bf16``: "reference rounding" of the CFG combine and the Euler update (icv_unpatchify_cfg_euler)."""
+        ``round_bf16``: "reference rounding" of the CFG combine and the Euler update (icv_unpatchify_cfg_euler).
+        ``tea_cache`` (teacache.TeaCachePlan): the steps it does not list as computed run no transformer blocks; they add the
+        residual the last computed step stored (one [n, d] f32 buffer per CFG branch).  None: every step is computed."""
         ops, plan = self.ops, self.plan
+        res = self._tc_residuals() if tea_cache is not None else None
         if branch_exchange is not None:
             if (ctx_cond is None) == (ctx_uncond is None) or cfg_scale == 1.0:
                 raise ValueError("cfg+sp: pass exactly one of ctx_cond / ctx_uncond and a cfg_scale != 1")
             own_ctx = ctx_cond if ctx_cond is not None else ctx_uncond
             for i in (steps if steps is not None else range(len(scheduler.sigmas))):
-                self.forward_tokens(latent, own_ctx, scheduler.timesteps[i], buf_tokens, self.head_own)
+                if res is not None and tea_cache.skip(i):
+                    self.forward_tokens(latent, own_ctx, scheduler.timesteps[i], res[0], self.head_own, num_layers=0)
+                else:
+                    self.forward_tokens(latent, own_ctx, scheduler.timesteps[i], buf_tokens, self.head_own)
+                    if res is not None:
+                        self._tc_store(self.patches, self.x, res[0])
                 branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
                 ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1], cfg_scale,
                                          scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
@@ -1038,7 +1062,12 @@ class WanDiT:
         twin, side = self._cfg_twin() if (use_cfg and self.dual_stream) else (None, None)
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
             ts = scheduler.timesteps[i]
-            if twin is not None:
+            if res is not None and tea_cache.skip(i):
+                # TeaCache: no blocks, so no K|V exchange either (every rank skips the same steps); both branches on this stream
+                self.forward_tokens(latent, ctx_cond, ts, res[0], self.head_out[0], num_layers=0)
+                if use_cfg:
+                    self.forward_tokens(latent, ctx_uncond, ts, res[1], self.head_out[1], num_layers=0)
+            elif twin is not None:
                 # the two CFG forwards are independent: the uncond one runs on a second HIP stream in a twin engine
                 # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
                 # filled by the other branch's kernels
@@ -1046,15 +1075,27 @@ class WanDiT:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     twin.forward_tokens(latent, ctx_uncond, ts, buf_tokens, self.head_out[1])
+                    if res is not None:
+                        self._tc_store(twin.patches, twin.x, res[1])
                 self.forward_tokens(latent, ctx_cond, ts, buf_tokens, self.head_out[0])
+                if res is not None:
+                    self._tc_store(self.patches, self.x, res[0])
                 main.wait_stream(side)
             elif use_cfg and self._pair_ok():
                 self.forward_pair(latent, ctx_cond, ctx_uncond, ts, buf_tokens, self.head_out, share_stem=self.share_stem)
+                if res is not None:      # the pair's stream holds the cond rows, then the uncond rows
+                    n = plan.n_tok
+                    self._tc_store(self.patches, self._pair.x[:n], res[0])
+                    self._tc_store(self.patches, self._pair.x[n:], res[1])
             else:
                 share = use_cfg and self.share_stem
                 self.forward_tokens(latent, ctx_cond, ts, buf_tokens, self.head_out[0], stem="save" if share else None)
+                if res is not None:
+                    self._tc_store(self.patches, self.x, res[0])
                 if use_cfg:
                     self.forward_tokens(latent, ctx_uncond, ts, buf_tokens, self.head_out[1], stem="load" if share else None)
+                    if res is not None:
+                        self._tc_store(self.patches, self.x, res[1])
             ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1] if use_cfg else None,
                                      cfg_scale, scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
             if self.sp_on:

@@ -49,7 +49,7 @@ import torch
 
 # pipeline attributes the caller may have changed since construction; sent with every request so the ranks cannot drift
 _PIPE_SETTINGS = ("num_inference_steps", "cfg_scale", "sigma_shift", "parallelism", "sp_chunks", "kv_exchange",
-                  "reference_rounding", "gemm_dtype", "attn_dtype")
+                  "reference_rounding", "gemm_dtype", "attn_dtype", "tea_cache_l1_thresh", "tea_cache_model_id")
 
 # what a rank reports about the environment its HIP runtime initialised under (WorkerPool.plan_record)
 _RANK_ENV_KEYS = ("GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY", "NCCL_MAX_NCHANNELS")
@@ -373,6 +373,10 @@ class WorkerPool:
             self.close(graceful=False)
             raise
         self.last_reply = done[0]
+        # TeaCache: the schedule the ranks ran (rank 0 built it and broadcast it), visible on the caller's pipeline as in one process
+        pipe.tea_cache_record = done[0].get("tea_cache_record")
+        if any(r.get("tea_cache_record") != pipe.tea_cache_record for r in done):
+            raise RuntimeError(f"WorkerPool.generate: the ranks ran different TeaCache schedules: {[r.get('tea_cache_record') for r in done]}")
         if done[0].get("kv_autotune") and os.environ.get("ICV_QUIET", "0") != "1":
             a = done[0]["kv_autotune"]
             print(f"[icvideo] K|V exchange autotune on the ranks: {a['chosen'][0]} x {a['chosen'][1]} chunks ({a['seconds']:.1f} s)", file=sys.stderr)
@@ -574,7 +578,7 @@ def worker_main() -> int:
             got = gen.pipe(prompt=c["prompt"], negative_prompt=c["negative_prompt"], semantic_buffer_video=gen._ndarray_to_pil_list(sem),
                            coordinate_buffer_video=gen._ndarray_to_pil_list(co), height=h, width=w, num_frames=n, seed=c["seed"],
                            tiled=c["tiled"], return_latents=rank != 0, join_decode=True)
-            reply = dict(rank=rank)
+            reply = dict(rank=rank, tea_cache_record=getattr(gen.pipe, "tea_cache_record", None))
             if rank == 0:
                 arr = np.stack([np.asarray(f) for f in got])
                 frames.write([arr])

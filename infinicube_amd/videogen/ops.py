@@ -377,3 +377,23 @@ class HipOps:
         assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel()
         native.check(self.lib.icv_cast_f32_to_bf16(src.data_ptr(), out.data_ptr(), src.numel(),
                                                    self._stream()), "icv_cast_f32_to_bf16")
+
+    # ---- TeaCache step skipping (teacache.py) ------------------------------------------------------
+    def sub_rows(self, x, r):
+        """r = x - r in place; x, r f32 [rows, d] (row strides allowed: halves of the pair engine, shard views)."""
+        _chk(x, F32, "sub_rows.x"); _chk(r, F32, "sub_rows.r")
+        if x.dim() != 2 or tuple(x.shape) != tuple(r.shape):
+            raise ValueError(f"sub_rows: shapes {tuple(x.shape)} and {tuple(r.shape)} differ (or are not [rows, d])")
+        rows, d = r.shape
+        native.check(self.lib.icv_sub_rows_f32(x.data_ptr(), x.stride(0), r.data_ptr(), r.stride(0), rows, d,
+                                               self._stream()), "icv_sub_rows_f32")
+
+    def rel_l1_steps(self, table, out):
+        """table f32 [N, cols] (one t_mod row per step) -> out f32 [N]: out[i] = mean|t_i - t_{i-1}| / mean|t_{i-1}|, out[0] = 0."""
+        _chk(table, F32, "rel_l1.table"); _chk(out, F32, "rel_l1.out")
+        if table.dim() != 2:
+            raise ValueError(f"rel_l1_steps: table must be [N, cols], got {tuple(table.shape)}")
+        n, cols = table.shape
+        assert out.is_contiguous() and out.numel() == n
+        native.check(self.lib.icv_rel_l1_steps_f32(table.data_ptr(), n, cols, table.stride(0), out.data_ptr(),
+                                                   self._stream()), "icv_rel_l1_steps_f32")

@@ -267,6 +267,13 @@ class WanVideoPipeline:
         # checkpoint was sampled with during fine-tuning validation).
         self.reference_rounding = os.environ.get("ICV_REFERENCE_ROUNDING", "0") == "1"
         self.scheduler = FlowMatchScheduler(self.num_inference_steps, self.sigma_shift, self.reference_rounding)
+        # TeaCache step skipping (teacache.py; upstream DiffSynth's keywords of the same names).  Off by default; the caller of the
+        # unchanged WanVideoGenerator opts in with ICV_TEACACHE_L1_THRESH (+ ICV_TEACACHE_MODEL_ID; without it a t2v DiT's id is
+        # inferred from its width).  pipe.tea_cache_record: the last call's schedule (None when it ran every step).
+        env_thresh = os.environ.get("ICV_TEACACHE_L1_THRESH")
+        self.tea_cache_l1_thresh: Optional[float] = float(env_thresh) if env_thresh else None
+        self.tea_cache_model_id = os.environ.get("ICV_TEACACHE_MODEL_ID", "")
+        self.tea_cache_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -398,6 +405,21 @@ class WanVideoPipeline:
         msk = msk.reshape(grid.T, 4, h // 8, w // 8).transpose(0, 1)                    # [4, T, h8, w8]
         return torch.cat([msk, lat], dim=0)
 
+    def _tea_cache_settings(self, thresh: Optional[float], model_id: str, cfg: WanDiTConfig):
+        """(threshold, model id) in effect for one call: the keyword, else the attribute (set from the environment at construction).
+        A threshold without an id raises DiffSynth's unknown-id error, except when both came from the environment: then a t2v
+        DiT's id follows from its width.  (None, "") = TeaCache off."""
+        from . import teacache
+        from_env = thresh is None and not model_id and "ICV_TEACACHE_L1_THRESH" in os.environ and not self.tea_cache_model_id
+        thresh = self.tea_cache_l1_thresh if thresh is None else thresh
+        model_id = model_id or self.tea_cache_model_id
+        if thresh is None:
+            return None, ""
+        if not model_id and from_env:
+            model_id = teacache.infer_t2v_model_id(cfg)
+        teacache.coefficients(model_id)          # validate before any work is done
+        return float(thresh), model_id
+
     # ---- D5: the generation call -----------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: str, negative_prompt: str = "", semantic_buffer_video=None,
@@ -405,7 +427,8 @@ class WanVideoPipeline:
                  seed: Optional[int] = None, tiled: bool = True, num_inference_steps: Optional[int] = None,
                  cfg_scale: Optional[float] = None, sigma_shift: Optional[float] = None, rand_device: str = "cpu",
                  tile_size=(30, 52), tile_stride=(15, 26), progress_bar_cmd=None, return_latents: bool = False,
-                 input_image=None, join_decode: bool = False, **unused):
+                 input_image=None, join_decode: bool = False, tea_cache_l1_thresh: Optional[float] = None,
+                 tea_cache_model_id: str = "", **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
@@ -414,6 +437,7 @@ class WanVideoPipeline:
         grid = TokenGrid(num_frames, height, width)
         engine = self._get_engine()
         ops = engine.ops
+        tc_thresh, tc_id = self._tea_cache_settings(tea_cache_l1_thresh, tea_cache_model_id, engine.cfg)
         world, rank = 1, 0
         from . import multigpu
         try:
@@ -497,13 +521,25 @@ class WanVideoPipeline:
             buf_tokens = engine.embed_cond_latents(y, add_to=buf_tokens)
         if tune_key is not None and tune_key not in self._kv_tuned:
             self._kv_tuned[tune_key] = self._autotune_kv(engine, latent, ctx_c if ctx_c is not None else ctx_u, buf_tokens, ops)
+        # TeaCache: the skip schedule of the whole call, decided on rank 0 and broadcast (every rank must skip the same steps, or the
+        # per-layer K|V exchange of a computed step would wait for a rank that skipped it)
+        tc_plan = None
+        if tc_thresh is not None:
+            from . import teacache
+            if rank == 0:
+                tc_plan = teacache.plan(engine, self.scheduler, tc_thresh, tc_id, range(num_inference_steps))
+            if world > 1:
+                box = [tc_plan]
+                dist.broadcast_object_list(box, src=0)
+                tc_plan = box[0]
+        self.tea_cache_record = tc_plan.record() if tc_plan is not None else None
         # the hot loop (HIP)
         it = range(num_inference_steps)
         if progress_bar_cmd is not None:
             it = progress_bar_cmd(it)
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
-                       round_bf16=self.reference_rounding)
+                       round_bf16=self.reference_rounding, tea_cache=tc_plan)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
         # The DECODE is sharded (a collective of every rank: vae.TileShard broadcasts the tiles) only where every rank is known to
         # take part: behind a multigpu.WorkerPool (its workers pass join_decode=True) or when the caller says so
