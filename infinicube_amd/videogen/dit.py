@@ -16,6 +16,8 @@ HBM layout, the step-invariant caches and the sequence-parallel schedule:
     kv_full  bf16 [S, 2d]       world > 1: the gathered rows of every rank (chunk-major, rank-major inside)
     att      bf16 [n, d]        attention output -> O-projection A operand
     ff       bf16 [n, ffn]      GELU(FFN1) output
+    _pair    the same x .. ff (and kv_loc, kv_full) with 2n rows: cond rows, then uncond rows, when the two CFG forwards of a
+                                step run as one batch (forward_pair); allocated on first use
     weights  bf16 [N, K]        torch Linear layout == the K-contiguous B operand of the MFMA GEMM
   Step-invariant caches: guidance-buffer tokens f32 [n, d] (once per generation; K1), text
   embedding + per-layer cross-attention K/V bf16 [L, text_len, d] per CFG branch (K9), RoPE tables.
@@ -71,6 +73,15 @@ class ContextKV:
     v: torch.Tensor  # bf16 [L, text_len, d]
     k_img: Optional[torch.Tensor] = None  # i2v: bf16 [L, img_len, d]
     v_img: Optional[torch.Tensor] = None
+
+
+@dataclass
+class _Branch:
+    """What differs between the forwards that share one workspace (the cond and the uncond forward of a CFG pair)."""
+    rows: slice                               # its rows of the workspace
+    ctx: ContextKV
+    kv_full: Optional[torch.Tensor] = None    # sequence parallel: where its gathered K|V rows land
+    kv8: Optional[tuple] = None               # ... and its e4m3 wire set (_sp_wire_set)
 
 
 class WanDiT:
@@ -176,6 +187,9 @@ class WanDiT:
         if buffer_embedder_sd is not None:
             self.load_buffer_embedder(buffer_embedder_sd)
         self.plan: Optional[ShardPlan] = None
+        # set by prepare(); here so that everything else reads them as plain attributes
+        self.kv_gather, self.kv8, self.fp8_wire, self.attn_arrival, self.sp_err = None, None, False, False, None
+        self._native, self._pair, self._twin = None, None, None
 
     # ------------------------------------------------------------------------------------
     def _quantize_weight(self, w: torch.Tensor):
@@ -312,7 +326,7 @@ class WanDiT:
         # chunked launches - _native_eligible() says no to the e4m3 wire format, the copy-engine transport and the arrival-driven
         # attention, and the per-op driver runs).  Off by default: host issue time is 0.3 % of a 14B step either way.
         self.native_forward = os.environ.get("ICV_NATIVE_FORWARD", "0") == "1"
-        if getattr(self, "_native", None) is not None:      # a new workspace: the old context points at freed buffers
+        if self._native is not None:      # a new workspace: the old context points at freed buffers
             self.ops.lib.icv_dit_destroy(self._native)
         self._native = None
         # ICV_SHARE_STEM=0 switches off the sharing of the context-free stem between the two CFG forwards (A/B, tests)
@@ -323,7 +337,7 @@ class WanDiT:
         self.cfg_batch = os.environ.get("ICV_CFG_BATCH", "1") == "1"
         self._pair = None
         if self.sp_on:
-            old = getattr(self, "kv_gather", None)
+            old = self.kv_gather
             if old is not None and old is not kv_gather and hasattr(old, "close"):
                 old.close()                                        # a copy-engine transport owns a heap and streams
             base_mode, arrival = split_kv_mode(kv_exchange)
@@ -338,8 +352,8 @@ class WanDiT:
             self.sp_acc = a((n, d), F32)                           # carried O accumulator between key chunks
             self.sp_ml = a((n, cfg.num_heads, 2), F32)             # carried (running max, row sum)
         else:
-            self.kv_loc, self.kv_full, self.kv_gather = None, None, None
-            self.attn_arrival, self.sp_err, self.sp_align = False, None, 1
+            self.kv_loc, self.kv_full, self.kv8, self.kv_gather = None, None, None, None
+            self.fp8_wire, self.attn_arrival, self.sp_err, self.sp_align = False, False, None, 1
         return self
 
     def _sp_local_rows(self):
@@ -351,14 +365,14 @@ class WanDiT:
         n, d, kg, H = self.plan.n_tok, self.cfg.dim, self.kv_gather, self.cfg.num_heads
         U8 = torch.uint8
         self._kv8_chunks, tot8 = [], 0
-        if getattr(self, "fp8_wire", False):
+        if self.fp8_wire:
             for b0, b1 in zip(self.sp_bounds[:-1], self.sp_bounds[1:]):
                 rows8 = self.ops.attention_fp8_blob_bytes(b1 - b0, H) // d          # blob as [rows8, d] bytes
                 self._kv8_chunks.append((tot8, rows8, b0, b1))
                 tot8 += rows8
         if hasattr(kg, "reserve"):
             kg.reserve(3 * n * 2 * d * 2 + 3 * tot8 * d + 4096, self.ops.device)
-        if getattr(self, "attn_arrival", False):
+        if self.attn_arrival:
             kg.enable_arrival(self.ops)      # after reserve(): the copy-engine transport's flags belong to its heap
         if hasattr(kg, "local_rows"):
             rows = lambda r, cols=2 * d, dt=BF16: kg.local_rows(r, cols, dt, self.ops.alloc)      # noqa: E731
@@ -367,7 +381,7 @@ class WanDiT:
         self.kv_loc = rows(n)
         self._kv_rows = rows
         self.kv8 = self._sp_wire_set(rows, tot8) if tot8 else None
-        if getattr(self, "_pair", None) is not None:
+        if self._pair is not None:
             self._pair.kv_loc = rows(2 * n)
             self._pair.kv8 = [self._sp_wire_set(rows, tot8) for _ in range(2)] if tot8 else None
 
@@ -399,7 +413,7 @@ class WanDiT:
     def _check_transport(self):
         """Per step, free (one host word): did a device-side wait of the K|V transport give up?  Then the rest of the loop would run on
         stale rows - stop now (the in-kernel waits fail fast after the first one, so a dead peer costs one deadline, not one per layer)."""
-        kg = getattr(self, "kv_gather", None)
+        kg = self.kv_gather
         if kg is not None and hasattr(kg, "check"):
             kg.check()
 
@@ -409,13 +423,13 @@ class WanDiT:
         4-byte read-back; never raises (seqpar.autotune_kv_exchange asks it after a candidate's warm-up: a transport whose data
         movement cannot make progress beside the WAITING attention work-groups - a starved RCCL channel kernel - shows up here, and
         the candidate is dropped on every rank)."""
-        kg = getattr(self, "kv_gather", None)
+        kg = self.kv_gather
         if kg is not None and hasattr(kg, "check"):
             try:
                 kg.check()
             except RuntimeError as e:
                 return str(e)
-        err = getattr(self, "sp_err", None)
+        err = self.sp_err
         if err is not None:
             e = int(err.item()) & 0xffffffff
             if e:
@@ -452,7 +466,7 @@ class WanDiT:
         if self.attn_fp8:      # the e4m3 K/V side of the workspace is sized for the largest gathered chunk
             kv_rows = self.plan.world * max(b1 - b0 for b0, b1 in zip(self.sp_bounds[:-1], self.sp_bounds[1:]))
             self.attn8_ws = self.ops.attention_fp8_buffers(n, kv_rows, self.cfg.dim, self.cfg.num_heads)
-        if getattr(self, "_native", None) is not None:      # the C driver's context holds the old bounds / communicator
+        if self._native is not None:      # the C driver's context holds the old bounds / communicator
             self.ops.lib.icv_dit_destroy(self._native)
             self._native = None
         return self
@@ -521,7 +535,7 @@ class WanDiT:
     def _drop_native_context(self):
         """The communicator the C driver's context points at is going away (seqpar._NativeComm.close): destroy the context; the
         next native forward rebuilds it against a live communicator or fails in icv_comm_create, never in a freed handle."""
-        h, self._native = getattr(self, "_native", None), None
+        h, self._native = self._native, None
         self._native_comm = None
         if h is not None:
             try:
@@ -536,7 +550,7 @@ class WanDiT:
         # on the wire, the copy-engine transport or the arrival-driven attention the per-op driver runs (it used to take
         # the C path and silently re-quantise gathered bf16 rows per chunk)
         sp_ok = not self.sp_on or (isinstance(self.kv_gather, KVGather) and self.kv_gather.mode != "ipc"
-                                   and not getattr(self, "fp8_wire", False) and not getattr(self, "attn_arrival", False))
+                                   and not self.fp8_wire and not self.attn_arrival)
         return self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok
 
     def native_profile(self, enable: bool):
@@ -575,7 +589,7 @@ class WanDiT:
         world, b, d = self.plan.world, self.sp_bounds, self.cfg.dim
         kv_loc = self.kv_loc if kv_loc is None else kv_loc
         handles, bufs = [], []
-        if getattr(self, "fp8_wire", False):
+        if self.fp8_wire:
             loc8, full8, amax = self.kv8 if kv8 is None else kv8
             H = self.cfg.num_heads
             if start:
@@ -606,7 +620,7 @@ class WanDiT:
         ops = self.ops
         att = self.att if att is None else att
         C = len(bufs)
-        if getattr(self, "attn_arrival", False) and not getattr(self, "fp8_wire", False):
+        if self.attn_arrival and not self.fp8_wire:
             # ONE launch over the pieces: this rank's own rows (in place, no flag) first, then every (row chunk, peer) in the order the
             # exchange delivers them - chunk-major, peers starting with the right-hand neighbour (the order the pulls are issued in)
             d, kg, world, rank = self.cfg.dim, self.kv_gather, self.plan.world, self.plan.rank
@@ -623,13 +637,13 @@ class WanDiT:
             for c in range(C if not from_memory else 0):
                 kg.consumed(handles[c])
             return
-        wire = getattr(self, "fp8_wire", False)
+        wire = self.fp8_wire
         ws = self.attn8_ws
         if ws is not None:
             if wire:
                 ws = ops.attention_fp8_with_amax(ws, bufs[0][2])     # this branch's abs-max table (queries' row written here)
             ops.attention_fp8_prepare(ws, H, q=q)                       # queries once per layer, under the first transfer
-        gated = wire and getattr(self, "attn_arrival", False)
+        gated = wire and self.attn_arrival
         for c in range(C):
             if not from_memory and not gated:
                 self.kv_gather.wait(handles[c])
@@ -763,13 +777,8 @@ class WanDiT:
         bit-identical values there.  "save" keeps the residual stream after that block in ``self.x_stem``; "load" starts
         from it instead of recomputing (denoise() does this for the second CFG forward: 1/80 of a step's self-attention,
         QKV and O work, same numbers)."""
-        cfg, ops, plan = self.cfg, self.ops, self.plan
-        d, H, n, eps = cfg.dim, cfg.num_heads, plan.n_tok, cfg.eps
-        scale = self.attn_scale          # = ln 2: K already carries (1/sqrt(hd)) * log2(e)
-        if (self.cond_w is not None) and buf_tokens is None:
-            raise ValueError("i2v DiT: pass the cached embed_cond_latents(y) tokens as buf_tokens")
-        if cfg.has_image_input != (ctx.k_img is not None):
-            raise ValueError("context was encoded without/with CLIP features but the DiT is/isn't i2v")
+        cfg, ops = self.cfg, self.ops
+        self._check_inputs(buf_tokens, ctx)
         self._time_state(timestep)
         if stem not in (None, "save", "load"):
             raise ValueError(f"stem must be None, 'save' or 'load', got {stem!r}")
@@ -792,80 +801,121 @@ class WanDiT:
             return
         self._forward_body(latent, ctx, buf_tokens, head_out, num_layers, stem)
 
+    def _check_inputs(self, buf_tokens, *ctxs):
+        if (self.cond_w is not None) and buf_tokens is None:
+            raise ValueError("i2v DiT: pass the cached embed_cond_latents(y) tokens as buf_tokens")
+        for ctx in ctxs:
+            if self.cfg.has_image_input != (ctx.k_img is not None):
+                raise ValueError("context was encoded without/with CLIP features but the DiT is/isn't i2v")
+
     def _forward_body(self, latent, ctx, buf_tokens, head_out, num_layers, stem=None):
         """The launch sequence of one forward after the time state: patch embed, L blocks, head."""
-        cfg, ops, plan = self.cfg, self.ops, self.plan
-        d, H, n, eps = cfg.dim, cfg.num_heads, plan.n_tok, cfg.eps
-        scale = self.attn_scale
         if self._native_eligible():
             from .. import native
+            ops = self.ops
             C, _, H8, W8 = latent.shape
             ki, vi = (ctx.k_img, ctx.v_img) if ctx.k_img is not None else (None, None)
             native.check(ops.lib.icv_dit_forward(
                 self._native_ctx(), latent.data_ptr(), C, H8, W8, self.mod.data_ptr(), self.hmod.data_ptr(), ctx.k.data_ptr(),
                 ctx.v.data_ptr(), ctx.k.shape[1], ctx.k.stride(0), native.ptr(ki), native.ptr(vi), ki.shape[1] if ki is not None else 0,
                 ki.stride(0) if ki is not None else 0, native.ptr(buf_tokens), head_out.data_ptr(),
-                -1 if num_layers is None else num_layers, {None: 0, "save": 1, "load": 2}[stem], scale, ops._stream()), "icv_dit_forward")
+                -1 if num_layers is None else num_layers, {None: 0, "save": 1, "load": 2}[stem], self.attn_scale, ops._stream()), "icv_dit_forward")
             return
+        branch = _Branch(slice(0, self.plan.n_tok), ctx, self.kv_full, self.kv8)
         if stem == "load":
             self.x.copy_(self.x_stem)          # the residual stream after layer 0's self-attention block (see forward_tokens)
         else:
-            # K1: patch embed (+ cached guidance-buffer tokens fused into the GEMM epilogue)
-            ops.patchify(latent, self.patches, plan.tok0, n)
-            if buf_tokens is not None:
-                ops.gemm(self.patches, self.patch_w, self.patch_b, self.x, EPI_RESID_F32, resid=buf_tokens)
-            else:
-                ops.gemm(self.patches, self.patch_w, self.patch_b, self.x, EPI_F32)
-        q, k, v = self.qkv[0], self.qkv[1], self.qkv[2]
-        L = cfg.num_layers if num_layers is None else num_layers
+            self._patch_embed(latent, buf_tokens, self.x)
+        self._blocks(self, [branch], self.cfg.num_layers if num_layers is None else num_layers,
+                     stem=0 if stem == "load" else 1,
+                     after_stem=(lambda: self.x_stem.copy_(self.x)) if stem == "save" else None)
+        self._head(self, head_out)
+
+    def _patch_embed(self, latent, buf_tokens, x):
+        """K1: patch embed (+ cached guidance-buffer tokens fused into the GEMM epilogue)."""
+        ops = self.ops
+        ops.patchify(latent, self.patches, self.plan.tok0, self.plan.n_tok)
+        if buf_tokens is not None:
+            ops.gemm(self.patches, self.patch_w, self.patch_b, x, EPI_RESID_F32, resid=buf_tokens)
+        else:
+            ops.gemm(self.patches, self.patch_w, self.patch_b, x, EPI_F32)
+
+    def _head(self, t, head_out):
+        """K11: head over every row of the workspace ``t``."""
+        self.ops.ln_modulate(t.x, t.h, shift=self.hmod[0], scale=self.hmod[1], eps=self.cfg.eps)
+        self.ops.gemm(t.h, self.head_w, self.head_b, head_out, EPI_F32)
+
+    def _blocks(self, t, branches, L, stem, after_stem=None):
+        """The transformer blocks 0 .. L-1, stated ONCE for a single forward and for the CFG-batched pair.  ``t``: the engine whose
+        workspace the rows live in (``self``, or the 2n-row ``_pair_engine()``); ``branches``: the forwards that share it - their
+        row ranges tile the workspace in order.  The token-local ops (LayerNorm, the six projections) run once over all rows;
+        RoPE, the K|V exchange, self-attention and cross-attention run per branch.  The transport, chunk bounds, RoPE table and
+        the carried attention state are read from ``self``: set_kv_exchange() replaces them on the engine that was prepared.
+        ``stem``: layer 0's self-attention block runs for the first ``stem`` branches only (it sees nothing of the context, so one
+        branch's rows can stand for the others: forward_tokens(stem=), forward_pair(share_stem=)); ``after_stem()`` runs right
+        behind that block."""
+        cfg, ops, plan = self.cfg, self.ops, self.plan
+        d, H, eps, scale = cfg.dim, cfg.num_heads, cfg.eps, self.attn_scale      # scale = ln 2: K already carries (1/sqrt(hd)) * log2(e)
+        q, k, v = t.qkv[0], t.qkv[1], t.qkv[2]
+        views = [(b, q[b.rows], k[b.rows], v[b.rows], t.att[b.rows]) for b in branches]      # once per forward, not per layer
         for i in range(L):
             lw = self.layers[i]
             m = self.mod[i]
             sh1, sc1, g1 = m[0:d], m[d:2 * d], m[2 * d:3 * d]
             sh2, sc2, g2 = m[3 * d:4 * d], m[4 * d:5 * d], m[5 * d:6 * d]
             # --- self-attention ---
-            if i == 0 and stem == "load":
-                pass                                                                        # taken from the cond forward
-            elif self.sp_on:
-                h = self._norm(lw["wqkv"], shift=sh1, scale=sc1, eps=eps)                   # K3
-                self._sp_acquire()
-                # K and V first, so their all-gather (K13) is already moving while Q is projected
-                self._mm(h, lw["wqkv"], lw["bqkv"], self.kv_loc, EPI_BF16, rows=slice(d, 3 * d))            # K4 (k | v rows)
-                ops.rmsnorm_rope(self.kv_loc[:, :d], lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)      # K5 (k)
-                handles, bufs = self._sp_start_gather()
-                self._mm(h, lw["wqkv"], lw["bqkv"], q, EPI_BF16, rows=slice(0, d))                   # K4 (q)
-                ops.rmsnorm_rope(q, lw["nq"], eps=eps, rope=self.rope, tok0=plan.tok0)               # K5 (q)
-                self._sp_attention(q, handles, bufs, H, scale)                                       # K6
-            else:
-                h = self._norm(lw["wqkv"], shift=sh1, scale=sc1, eps=eps)                   # K3
-                self._mm(h, lw["wqkv"], lw["bqkv"], self.qkv, EPI_BF16, nsplit=d)           # K4
-                ops.rmsnorm_rope(q, lw["nq"], k, lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)  # K5
-                if self.attn8_ws is not None:
-                    ops.attention_fp8(q, k, v, self.att, H, self.attn8_ws)                  # K6 (e4m3)
+            active = views[:stem] if i == 0 else views
+            if active:
+                rs = slice(0, active[-1][0].rows.stop)
+                xs = t.x[rs]
+                h = t._norm(lw["wqkv"], rows=rs, shift=sh1, scale=sc1, eps=eps)                               # K3
+                if self.sp_on:
+                    # sequence parallel: the projections run once over the rows of every branch - at n = 4 680 (sp8, 14B) the
+                    # N = 5120 GEMMs of a pair go from 2 x 380 tiles = 2 x 1.48 rounds of 256 CUs to 740 tiles = 2.89 rounds - while
+                    # exchange and attention stay per branch: the uncond rows travel under the cond branch's attention
+                    self._sp_acquire()
+                    # K and V first, so their all-gather (K13) is already moving while Q is projected
+                    t._mm(h, lw["wqkv"], lw["bqkv"], t.kv_loc[rs], EPI_BF16, rows=slice(d, 3 * d))            # K4 (k | v rows)
+                    pend = []
+                    for b, *_ in active:
+                        kv = t.kv_loc[b.rows]
+                        ops.rmsnorm_rope(kv[:, :d], lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)        # K5 (k)
+                        pend.append(self._sp_start_gather(kv, b.kv_full, b.kv8))                              # K13
+                    t._mm(h, lw["wqkv"], lw["bqkv"], q[rs], EPI_BF16, rows=slice(0, d))                       # K4 (q)
+                    for (_, qb, _, _, ab), (handles, bufs) in zip(active, pend):
+                        ops.rmsnorm_rope(qb, lw["nq"], eps=eps, rope=self.rope, tok0=plan.tok0)               # K5 (q)
+                        self._sp_attention(qb, handles, bufs, H, scale, att=ab)                               # K6
                 else:
-                    ops.attention(q, k, v, self.att, H, scale)                              # K6
-            if not (i == 0 and stem == "load"):
-                a = self._operand(self.att, self.att8, self.att8s, lw["wo"])
-                self._mm(a, lw["wo"], lw["bo"], self.x, EPI_RESID_F32, resid=self.x, gate=g1)   # K7
-                if i == 0 and stem == "save":
-                    self.x_stem.copy_(self.x)
-            # --- cross-attention to text (no gate) ---
-            h = self._norm(lw["xq_w"], weight=lw["n3w"], bias=lw["n3b"], eps=eps)           # K8
-            self._mm(h, lw["xq_w"], lw["xq_b"], q, EPI_BF16)                                # K9
+                    if len(active) == len(views):
+                        t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv, EPI_BF16, nsplit=d)                           # K4
+                    else:   # some of the rows of each plane: three plain GEMMs keep the [3, rows, d] plane layout
+                        for j in range(3):
+                            t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv[j][rs], EPI_BF16, rows=slice(j * d, (j + 1) * d))
+                    for _, qb, kb, vb, ab in active:
+                        ops.rmsnorm_rope(qb, lw["nq"], kb, lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)  # K5
+                        if self.attn8_ws is not None:
+                            ops.attention_fp8(qb, kb, vb, ab, H, self.attn8_ws)                               # K6 (e4m3)
+                        else:
+                            ops.attention(qb, kb, vb, ab, H, scale)                                           # K6
+                a = t._operand(t.att, t.att8, t.att8s, lw["wo"], rows=rs)
+                t._mm(a, lw["wo"], lw["bo"], xs, EPI_RESID_F32, resid=xs, gate=g1)                            # K7
+            if i == 0 and after_stem is not None:
+                after_stem()
+            # --- cross-attention (no gate): one projection, each branch against its own context ---
+            h = t._norm(lw["xq_w"], weight=lw["n3w"], bias=lw["n3b"], eps=eps)                                # K8
+            t._mm(h, lw["xq_w"], lw["xq_b"], q, EPI_BF16)                                                     # K9
             ops.rmsnorm_rope(q, lw["xnq"], eps=eps)
-            ops.attention(q, ctx.k[i], ctx.v[i], self.att, H, scale)
-            if ctx.k_img is not None:                                                      # i2v: + softmax over CLIP tokens
-                ops.attention_add(q, ctx.k_img[i], ctx.v_img[i], self.att, H, scale)
-            a = self._operand(self.att, self.att8, self.att8s, lw["xo_w"])
-            self._mm(a, lw["xo_w"], lw["xo_b"], self.x, EPI_RESID_F32, resid=self.x)
+            for b, qb, _, _, ab in views:
+                ops.attention(qb, b.ctx.k[i], b.ctx.v[i], ab, H, scale)
+                if b.ctx.k_img is not None:                                                                   # i2v: + softmax over CLIP tokens
+                    ops.attention_add(qb, b.ctx.k_img[i], b.ctx.v_img[i], ab, H, scale)
+            a = t._operand(t.att, t.att8, t.att8s, lw["xo_w"])
+            t._mm(a, lw["xo_w"], lw["xo_b"], t.x, EPI_RESID_F32, resid=t.x)
             # --- FFN ---
-            h = self._norm(lw["f0_w"], shift=sh2, scale=sc2, eps=eps)                       # K3
-            self._mm(h, lw["f0_w"], lw["f0_b"], self.ff, EPI_GELU_BF16)                     # K10
-            a = self._operand(self.ff, self.ff8, self.ff8s, lw["f2_w"])
-            self._mm(a, lw["f2_w"], lw["f2_b"], self.x, EPI_RESID_F32, resid=self.x, gate=g2)
-        # K11: head
-        ops.ln_modulate(self.x, self.h, shift=self.hmod[0], scale=self.hmod[1], eps=eps)
-        ops.gemm(self.h, self.head_w, self.head_b, head_out, EPI_F32)
+            h = t._norm(lw["f0_w"], shift=sh2, scale=sc2, eps=eps)                                            # K3
+            t._mm(h, lw["f0_w"], lw["f0_b"], t.ff, EPI_GELU_BF16)                                             # K10
+            a = t._operand(t.ff, t.ff8, t.ff8s, lw["f2_w"])
+            t._mm(a, lw["f2_w"], lw["f2_b"], t.x, EPI_RESID_F32, resid=t.x, gate=g2)
 
     # ------------------------------------------------------------------------------------
     # CFG-batched forward pair (single rank): the cond and uncond forwards of a step as ONE batch of 2n rows through every
@@ -881,13 +931,18 @@ class WanDiT:
         return (self.cfg_batch and not self._graphs_on and not self._native_eligible() and not self.dual_stream
                 and n2 * max(self.cfg.dim, self.cfg.ffn_dim) * 2 <= self.PAIR_MAX_OPERAND_BYTES)
 
+    def _engine_copy(self):
+        """Shallow copy of this engine (weights and caches by reference) that owns nothing of this one's per-workspace state."""
+        import copy
+        t = copy.copy(self)
+        t._pair, t._twin, t._native, t._graphs, t._graphs_on = None, None, None, {}, False
+        return t
+
     def _pair_engine(self):
         """Twin of this engine whose workspace holds 2n rows (weights and caches by reference)."""
-        if getattr(self, "_pair", None) is None:
-            import copy
+        if self._pair is None:
             cfg, a, n2, d = self.cfg, self.ops.alloc, 2 * self.plan.n_tok, self.cfg.dim
-            t = copy.copy(self)
-            t._pair, t._twin, t._native, t._graphs, t._graphs_on, t.native_forward = None, None, None, {}, False, False
+            t = self._engine_copy()
             t.x, t.h, t.qkv = a((n2, d), F32), a((n2, d), BF16), a((3, n2, d), BF16)
             t.att, t.ff = a((n2, d), BF16), a((n2, cfg.ffn_dim), BF16)
             if self.fp8:
@@ -906,103 +961,25 @@ class WanDiT:
         """Both CFG forwards of a step: head_out2 f32 [2, n, out_dim*4] (slot 0 = cond, 1 = uncond).  ``share_stem``: layer 0's
         self-attention block is computed once on n rows (it sees nothing of the context) and duplicated, as
         forward_tokens(stem="save" / "load") does for sequential forwards."""
-        cfg, ops, plan = self.cfg, self.ops, self.plan
-        d, H, n, eps, scale = cfg.dim, cfg.num_heads, plan.n_tok, cfg.eps, self.attn_scale
-        if (self.cond_w is not None) and buf_tokens is None:
-            raise ValueError("i2v DiT: pass the cached embed_cond_latents(y) tokens as buf_tokens")
-        for ctx in (ctx_c, ctx_u):
-            if cfg.has_image_input != (ctx.k_img is not None):
-                raise ValueError("context was encoded without/with CLIP features but the DiT is/isn't i2v")
+        n = self.plan.n_tok
+        self._check_inputs(buf_tokens, ctx_c, ctx_u)
         self._time_state(timestep)
         t = self._pair_engine()
-        t.mod, t.hmod = self.mod, self.hmod
-        halves = (slice(0, n), slice(n, 2 * n))
-        # K1 once: both branches start from the same tokens
-        ops.patchify(latent, self.patches, plan.tok0, n)
-        if buf_tokens is not None:
-            ops.gemm(self.patches, self.patch_w, self.patch_b, t.x[halves[0]], EPI_RESID_F32, resid=buf_tokens)
-        else:
-            ops.gemm(self.patches, self.patch_w, self.patch_b, t.x[halves[0]], EPI_F32)
-        q, k, v = t.qkv[0], t.qkv[1], t.qkv[2]
-
-        def self_attention_block(lw, sh1, sc1, g1, rows_list, rows_all):
-            h = t._norm(lw["wqkv"], rows=rows_all, shift=sh1, scale=sc1, eps=eps)                       # K3
-            if self.sp_on:
-                # sequence parallel ("sp" layout: this rank runs BOTH forwards of a step on its token shard): the projections run
-                # once over the 2n rows of the pair - at n = 4 680 (sp8, 14B) the N = 5120 GEMMs go from 2 x 380 tiles = 2 x 1.48
-                # rounds of 256 CUs to 740 tiles = 2.89 rounds - while exchange and attention stay per branch: the uncond rows
-                # travel under the cond branch's attention
-                rs = slice(0, 2 * n) if rows_all is None else rows_all
-                self._sp_acquire()
-                t._mm(h, lw["wqkv"], lw["bqkv"], t.kv_loc[rs], EPI_BF16, rows=slice(d, 3 * d))            # K4 (k | v rows)
-                pend = []
-                for bi, r in enumerate(halves):
-                    if r not in rows_list:
-                        continue
-                    ops.rmsnorm_rope(t.kv_loc[r][:, :d], lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)   # K5 (k)
-                    pend.append((r,) + self._sp_start_gather(t.kv_loc[r], t.kv_full[bi], t.kv8[bi] if t.kv8 is not None else None))   # K13
-                t._mm(h, lw["wqkv"], lw["bqkv"], q[rs], EPI_BF16, rows=slice(0, d))                       # K4 (q)
-                for r, handles, bufs in pend:
-                    ops.rmsnorm_rope(q[r], lw["nq"], eps=eps, rope=self.rope, tok0=plan.tok0)             # K5 (q)
-                    self._sp_attention(q[r], handles, bufs, H, scale, att=t.att[r])                       # K6
-                a = t._operand(t.att, t.att8, t.att8s, lw["wo"], rows=rows_all)
-                xr = t.x if rows_all is None else t.x[rows_all]
-                t._mm(a, lw["wo"], lw["bo"], xr, EPI_RESID_F32, resid=xr, gate=g1)                        # K7
-                return
-            if rows_all is None:
-                t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv, EPI_BF16, nsplit=d)                             # K4, 2n rows
-            else:   # n rows into the first half of each plane: three plain GEMMs keep the [3, 2n, d] plane layout
-                for j in range(3):
-                    t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv[j][rows_all], EPI_BF16, rows=slice(j * d, (j + 1) * d))
-            for r in rows_list:
-                ops.rmsnorm_rope(q[r], lw["nq"], k[r], lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)   # K5
-                if self.attn8_ws is not None:
-                    ops.attention_fp8(q[r], k[r], v[r], t.att[r], H, self.attn8_ws)                     # K6 (e4m3)
-                else:
-                    ops.attention(q[r], k[r], v[r], t.att[r], H, scale)                                 # K6
-            a = t._operand(t.att, t.att8, t.att8s, lw["wo"], rows=rows_all)
-            xr = t.x if rows_all is None else t.x[rows_all]
-            t._mm(a, lw["wo"], lw["bo"], xr, EPI_RESID_F32, resid=xr, gate=g1)                          # K7
-
-        for i in range(cfg.num_layers):
-            lw = self.layers[i]
-            m = self.mod[i]
-            sh1, sc1, g1 = m[0:d], m[d:2 * d], m[2 * d:3 * d]
-            sh2, sc2, g2 = m[3 * d:4 * d], m[4 * d:5 * d], m[5 * d:6 * d]
-            if i == 0 and share_stem:
-                self_attention_block(lw, sh1, sc1, g1, [halves[0]], halves[0])
-                t.x[halves[1]].copy_(t.x[halves[0]])
-            else:
-                if i == 0:
-                    t.x[halves[1]].copy_(t.x[halves[0]])
-                self_attention_block(lw, sh1, sc1, g1, halves, None)
-            # --- cross-attention: one projection over 2n rows, each half against its own context ---
-            h = t._norm(lw["xq_w"], weight=lw["n3w"], bias=lw["n3b"], eps=eps)                          # K8
-            t._mm(h, lw["xq_w"], lw["xq_b"], q, EPI_BF16)                                               # K9
-            ops.rmsnorm_rope(q, lw["xnq"], eps=eps)
-            for r, ctx in zip(halves, (ctx_c, ctx_u)):
-                ops.attention(q[r], ctx.k[i], ctx.v[i], t.att[r], H, scale)
-                if ctx.k_img is not None:
-                    ops.attention_add(q[r], ctx.k_img[i], ctx.v_img[i], t.att[r], H, scale)
-            a = t._operand(t.att, t.att8, t.att8s, lw["xo_w"])
-            t._mm(a, lw["xo_w"], lw["xo_b"], t.x, EPI_RESID_F32, resid=t.x)
-            # --- FFN over 2n rows ---
-            h = t._norm(lw["f0_w"], shift=sh2, scale=sc2, eps=eps)                                      # K3
-            t._mm(h, lw["f0_w"], lw["f0_b"], t.ff, EPI_GELU_BF16)                                       # K10
-            a = t._operand(t.ff, t.ff8, t.ff8s, lw["f2_w"])
-            t._mm(a, lw["f2_w"], lw["f2_b"], t.x, EPI_RESID_F32, resid=t.x, gate=g2)
-        # K11: head over 2n rows
-        ops.ln_modulate(t.x, t.h, shift=self.hmod[0], scale=self.hmod[1], eps=eps)
-        ops.gemm(t.h, self.head_w, self.head_b, head_out2.view(2 * n, -1), EPI_F32)
+        branches = [_Branch(slice(bi * n, (bi + 1) * n), ctx, t.kv_full[bi] if self.sp_on else None, t.kv8[bi] if t.kv8 is not None else None)
+                    for bi, ctx in enumerate((ctx_c, ctx_u))]
+        first, second = t.x[branches[0].rows], t.x[branches[1].rows]
+        self._patch_embed(latent, buf_tokens, first)      # K1 once: both branches start from the same tokens
+        if not share_stem:
+            second.copy_(first)
+        self._blocks(t, branches, self.cfg.num_layers, stem=1 if share_stem else 2,
+                     after_stem=(lambda: second.copy_(first)) if share_stem else None)
+        self._head(t, head_out2.view(2 * n, -1))
 
     # ------------------------------------------------------------------------------------
     def _cfg_twin(self):
         """Second engine for the dual-stream CFG mode: shares every weight tensor, owns a workspace and a stream."""
-        if getattr(self, "_twin", None) is None:
-            import copy
-            twin = copy.copy(self)                      # shallow: weights / caches by reference
-            twin._twin = None
-            twin._native = None                         # its own workspace -> its own native context, if any
+        if self._twin is None:
+            twin = self._engine_copy()                  # its own workspace -> its own native context, if any
             twin.dual_stream = False
             twin.prepare(self.grid, self.plan, graphs=False)
             self._twin = (twin, torch.cuda.Stream(device=self.ops.device))
@@ -1023,6 +1000,36 @@ class WanDiT:
         self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
         self.ops.sub_rows(x, r)
 
+    def _computed_step(self, latent, ctxs, ts, buf_tokens, outs):
+        """The forwards of one step that runs the blocks, in the mode this engine is set up for: one forward per context of
+        ``ctxs`` into the matching head output of ``outs``.  A generator: yields (branch, patches, x rows) as soon as that
+        branch's residual stream is final and before anything overwrites it - what _tc_store needs; the consumer's work runs
+        on the stream that branch ran on."""
+        pair = len(ctxs) == 2
+        if pair and self.dual_stream:
+            # the two CFG forwards are independent: the uncond one runs on a second HIP stream in a twin engine
+            # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
+            # filled by the other branch's kernels
+            twin, side = self._cfg_twin()
+            main = torch.cuda.current_stream(self.ops.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                twin.forward_tokens(latent, ctxs[1], ts, buf_tokens, outs[1])
+                yield 1, twin.patches, twin.x
+            self.forward_tokens(latent, ctxs[0], ts, buf_tokens, outs[0])
+            yield 0, self.patches, self.x
+            main.wait_stream(side)
+        elif pair and self._pair_ok():
+            n = self.plan.n_tok
+            self.forward_pair(latent, ctxs[0], ctxs[1], ts, buf_tokens, self.head_out, share_stem=self.share_stem)
+            yield 0, self.patches, self._pair.x[:n]      # the pair's stream holds the cond rows, then the uncond rows
+            yield 1, self.patches, self._pair.x[n:]
+        else:
+            share = pair and self.share_stem
+            for b, (ctx, out) in enumerate(zip(ctxs, outs)):
+                self.forward_tokens(latent, ctx, ts, buf_tokens, out, stem=("save", "load")[b] if share else None)
+                yield b, self.patches, self.x
+
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
@@ -1040,62 +1047,22 @@ class WanDiT:
         if branch_exchange is not None:
             if (ctx_cond is None) == (ctx_uncond is None) or cfg_scale == 1.0:
                 raise ValueError("cfg+sp: pass exactly one of ctx_cond / ctx_uncond and a cfg_scale != 1")
-            own_ctx = ctx_cond if ctx_cond is not None else ctx_uncond
-            for i in (steps if steps is not None else range(len(scheduler.sigmas))):
-                if res is not None and tea_cache.skip(i):
-                    self.forward_tokens(latent, own_ctx, scheduler.timesteps[i], res[0], self.head_own, num_layers=0)
-                else:
-                    self.forward_tokens(latent, own_ctx, scheduler.timesteps[i], buf_tokens, self.head_own)
-                    if res is not None:
-                        self._tc_store(self.patches, self.x, res[0])
-                branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
-                ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1], cfg_scale,
-                                         scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
-                if self.sp_on:
-                    self._check_transport()
-                if on_step is not None:
-                    on_step(i, latent)
-            if self.sp_on:
-                self.check_exchange()
-            return latent
-        use_cfg = ctx_uncond is not None and cfg_scale != 1.0
-        twin, side = self._cfg_twin() if (use_cfg and self.dual_stream) else (None, None)
+            ctxs, outs, use_cfg = [ctx_cond if ctx_cond is not None else ctx_uncond], [self.head_own], True
+        else:
+            use_cfg = ctx_uncond is not None and cfg_scale != 1.0
+            ctxs, outs = [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], [self.head_out[0], self.head_out[1]]
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
             ts = scheduler.timesteps[i]
             if res is not None and tea_cache.skip(i):
                 # TeaCache: no blocks, so no K|V exchange either (every rank skips the same steps); both branches on this stream
-                self.forward_tokens(latent, ctx_cond, ts, res[0], self.head_out[0], num_layers=0)
-                if use_cfg:
-                    self.forward_tokens(latent, ctx_uncond, ts, res[1], self.head_out[1], num_layers=0)
-            elif twin is not None:
-                # the two CFG forwards are independent: the uncond one runs on a second HIP stream in a twin engine
-                # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
-                # filled by the other branch's kernels
-                main = torch.cuda.current_stream(ops.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    twin.forward_tokens(latent, ctx_uncond, ts, buf_tokens, self.head_out[1])
-                    if res is not None:
-                        self._tc_store(twin.patches, twin.x, res[1])
-                self.forward_tokens(latent, ctx_cond, ts, buf_tokens, self.head_out[0])
-                if res is not None:
-                    self._tc_store(self.patches, self.x, res[0])
-                main.wait_stream(side)
-            elif use_cfg and self._pair_ok():
-                self.forward_pair(latent, ctx_cond, ctx_uncond, ts, buf_tokens, self.head_out, share_stem=self.share_stem)
-                if res is not None:      # the pair's stream holds the cond rows, then the uncond rows
-                    n = plan.n_tok
-                    self._tc_store(self.patches, self._pair.x[:n], res[0])
-                    self._tc_store(self.patches, self._pair.x[n:], res[1])
+                for ctx, r, out in zip(ctxs, res, outs):
+                    self.forward_tokens(latent, ctx, ts, r, out, num_layers=0)
             else:
-                share = use_cfg and self.share_stem
-                self.forward_tokens(latent, ctx_cond, ts, buf_tokens, self.head_out[0], stem="save" if share else None)
-                if res is not None:
-                    self._tc_store(self.patches, self.x, res[0])
-                if use_cfg:
-                    self.forward_tokens(latent, ctx_uncond, ts, buf_tokens, self.head_out[1], stem="load" if share else None)
+                for b, patches, x in self._computed_step(latent, ctxs, ts, buf_tokens, outs):
                     if res is not None:
-                        self._tc_store(self.patches, self.x, res[1])
+                        self._tc_store(patches, x, res[b])
+            if branch_exchange is not None:
+                branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
             ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1] if use_cfg else None,
                                      cfg_scale, scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
             if self.sp_on:
