@@ -35,7 +35,8 @@ extern "C" {
  *    probe), icv_flag_write; no existing
  *    signature changed.
  * 5: icv_attention_fp8_fwd_pieces_gated (the e4m3 chunk launches gate on their pieces' arrival flags inside the kernel); no existing
- *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping). */
+ *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping);
+ *    icv_unpatchify_cfg_euler_window (sliding temporal windows). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -365,6 +366,8 @@ int icv_voxel_raycast(const int* vol, const unsigned char* bricks, const int* di
  *   one carried-state launch per row chunk.  The copy-engine transport (icv_ipc_*), e4m3 K|V on the wire
  *   (icv_attention_fp8_quantize_kv / _fwd_pieces) and the arrival-driven attention (icv_attention_fwd_pieces) are driven through
  *   the per-op entry points by the host (infinicube_amd/videogen/dit.py, which refuses the one-call driver in those modes).
+ *   Nor does it cover sliding temporal windows (icv_unpatchify_cfg_euler_window): icv_dit_forward patchifies from token 0 of the
+ *   latent it is given, a window starts at a frame offset inside the clip's latent, so the host runs the per-op driver there too.
  * icv_dit_forward: latent f32 [C,T,H8,W8]; mod f32 [layers,6d] and hmod f32 [2,d] = this step's modulation tables;
  *   ctx_k / ctx_v bf16 [ctx_len, d] of layer 0, layer i at + i * ctx_layer_stride elements (text K/V cache); img_k / img_v
  *   likewise with img_len / img_layer_stride, or NULL; buf_tokens f32
@@ -506,6 +509,22 @@ int icv_cast_f32_to_bf16(const float* in, void* out, int64_t n, void* stream);
  * every rank computes the same bits.  Replaces the per-step distance of upstream DiffSynth's TeaCache.check [EXT]. */
 int icv_sub_rows_f32(const float* x, int64_t ldx, float* r, int64_t ldr, int64_t rows, int64_t d, void* stream);
 int icv_rel_l1_steps_f32(const float* table, int64_t n, int64_t cols, int64_t ldt, float* out, void* stream);
+
+/* ---- sliding temporal windows: the end of a step for ONE window ------------------------------------------
+ * The DiT ran on latent frames [frame0, frame0 + Tw) of a [C, T, H8, W8] clip as a clip of its own; hc / hu f32 [n_w, 4*C] (ldh)
+ * are its head outputs, rows = window-local tokens.  For window-local token r in [tok0, tok0 + n_tok) (frame f, hp, wp; row
+ * r - tok0 of hc / hu): v = hu + cfg_scale * (hc - hu) (hu may be NULL -> v = hc), then
+ *   latent_next[c, frame0 + f, 2hp+y, 2wp+z] += frame_coef[f] * (v[(y*2+z)*C + c] * dsigma)      (exact f32, no fused multiply-add)
+ * frame_coef: device f32, one blend coefficient per frame of the window (videogen/sliding_window.py: the coefficients of the
+ * windows over a frame sum to 1).  latent_next starts a step as a copy of the step's input latent; the windows of a step are
+ * launched one after the other on one stream, so the accumulation order is fixed: deterministic, no atomics.  Nothing outside
+ * the window's frames and token range is touched.
+ * round_bf16 != 0: both model outputs, (hc - hu), cfg * (.), hu + (.) and v * dsigma are rounded to bf16 exactly as
+ * icv_unpatchify_cfg_euler does.  The weighting and the accumulation stay f32 - no bf16 pipeline materialises them in this
+ * order - so, unlike icv_unpatchify_cfg_euler, this entry does NOT round the updated latent. */
+int icv_unpatchify_cfg_euler_window(float* latent_next, const float* hc, const float* hu, int64_t ldh, float cfg_scale,
+                                    float dsigma, const float* frame_coef, int64_t frame0, int64_t C, int64_t T, int64_t H8,
+                                    int64_t W8, int64_t tok0, int64_t n_tok, int round_bf16, void* stream);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,7 @@ SIGNATURES.update({
     "icv_dit_profile_read": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     "icv_sub_rows_f32": (c_int, [_P, _I, _P, _I, _I, _I, _P]),
     "icv_rel_l1_steps_f32": (c_int, [_P, _I, _I, _I, _P, _P]),
+    "icv_unpatchify_cfg_euler_window": (c_int, [_P, _P, _P, _I, _F, _F, _P, _I, _I, _I, _I, _I, _I, _I, c_int, _P]),
 })
 
 class KVPiece(ctypes.Structure):

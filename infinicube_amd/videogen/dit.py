@@ -309,6 +309,9 @@ class WanDiT:
         self.t_mod = a((1, 6 * d), F32)
         self._t_cached = None
         self._tc_res = None                # TeaCache residuals, one f32 [n, d] per CFG branch (allocated on first use)
+        # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
+        # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
+        self._lat_tok0, self._win_engines, self._win_next = None, {}, None
         env = os.environ.get("ICV_GRAPHS")
         if env is not None:
             graphs = env == "1"
@@ -551,7 +554,8 @@ class WanDiT:
         # the C path and silently re-quantise gathered bf16 rows per chunk)
         sp_ok = not self.sp_on or (isinstance(self.kv_gather, KVGather) and self.kv_gather.mode != "ipc"
                                    and not self.fp8_wire and not self.attn_arrival)
-        return self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok
+        # ... and it patchifies from token 0 of the latent: a sliding window starts at a frame offset, so the per-op driver runs
+        return self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok and self._lat_tok0 is None
 
     def native_profile(self, enable: bool):
         """Time every self-attention launch of the native forward with HIP events on the launch stream (bench.py)."""
@@ -732,12 +736,17 @@ class WanDiT:
             ops.gemm(pt, self.cond_w, None, out, EPI_RESID_F32, resid=add_to)
         return out
 
-    def embed_buffers(self, buffer_latents: torch.Tensor) -> torch.Tensor:
-        """Guidance-buffer tokens f32 [n, d] for this shard (step-invariant)."""
+    def embed_buffers(self, buffer_latents: torch.Tensor, whole_clip: bool = False) -> torch.Tensor:
+        """Guidance-buffer tokens f32 [n, d] for this shard (step-invariant).
+        ``whole_clip`` (sliding temporal windows): the tokens of EVERY frame of ``buffer_latents`` [C, T_clip, H8, W8], f32
+        [T_clip * Hp * Wp, d], whatever grid the workspace was prepared for - a window's tokens are a row range of it."""
         if self.buffer_embedder is None:
             raise RuntimeError("buffer embedder not initialised")
         ops, plan = self.ops, self.plan
         bl = ops.to_device(buffer_latents, F32)
+        if whole_clip:
+            from types import SimpleNamespace
+            plan = SimpleNamespace(tok0=0, n_tok=bl.shape[1] * (bl.shape[2] // 2) * (bl.shape[3] // 2))
         out = ops.alloc((plan.n_tok, self.cfg.dim), F32)
         c0 = 0
         for j, cv in enumerate(self.buffer_embedder):
@@ -785,7 +794,8 @@ class WanDiT:
         if stem is not None and (num_layers == 0 or cfg.num_layers == 0):
             stem = None
         if self._graphs_on:
-            key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem)
+            # a window's offset into the latent is an argument of the captured patchify: part of the key
+            key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem, self._lat_tok0)
             entry = self._graphs.get(key)
             if entry is None:
                 # first call with these buffers: run eagerly (that IS this call's result; it also lets every kernel do
@@ -834,7 +844,7 @@ class WanDiT:
     def _patch_embed(self, latent, buf_tokens, x):
         """K1: patch embed (+ cached guidance-buffer tokens fused into the GEMM epilogue)."""
         ops = self.ops
-        ops.patchify(latent, self.patches, self.plan.tok0, self.plan.n_tok)
+        ops.patchify(latent, self.patches, self.plan.tok0 + (self._lat_tok0 or 0), self.plan.n_tok)
         if buf_tokens is not None:
             ops.gemm(self.patches, self.patch_w, self.patch_b, x, EPI_RESID_F32, resid=buf_tokens)
         else:
@@ -936,6 +946,7 @@ class WanDiT:
         import copy
         t = copy.copy(self)
         t._pair, t._twin, t._native, t._graphs, t._graphs_on = None, None, None, {}, False
+        t._lat_tok0, t._win_engines, t._win_next = None, {}, None
         return t
 
     def _pair_engine(self):
@@ -1011,6 +1022,7 @@ class WanDiT:
             # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
             # filled by the other branch's kernels
             twin, side = self._cfg_twin()
+            twin._lat_tok0 = self._lat_tok0
             main = torch.cuda.current_stream(self.ops.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -1033,7 +1045,7 @@ class WanDiT:
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
-                branch_exchange=None, round_bf16: bool = False, tea_cache=None) -> torch.Tensor:
+                branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1041,8 +1053,20 @@ class WanDiT:
         tokens with the rank that runs the other branch on the same token shard.
         ``round_bf16``: "reference rounding" of the CFG combine and the Euler update (icv_unpatchify_cfg_euler).
         ``tea_cache`` (teacache.TeaCachePlan): the steps it does not list as computed run no transformer blocks; they add the
-        residual the last computed step stored (one [n, d] f32 buffer per CFG branch).  None: every step is computed."""
+        residual the last computed step stored (one [n, d] f32 buffer per CFG branch).  None: every step is computed.
+        ``sliding_window`` (sliding_window.WindowPlan over the T frames of ``latent``): with more than one window, every step runs
+        the forwards on each temporal window and blends their updates (_denoise_windows); this engine must be prepared for a
+        window's grid, ``buf_tokens`` are the whole clip's (embed_buffers(whole_clip=True)).  None or ONE window: this loop."""
         ops, plan = self.ops, self.plan
+        if sliding_window is not None and len(sliding_window.windows) > 1:
+            for on, what in ((self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)"),
+                             (self.cond_w is not None, "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)"),
+                             (tea_cache is not None, "TeaCache (one residual per window and CFG branch is not implemented)")):
+                if on:
+                    raise ValueError(f"sliding temporal windows cannot be combined with {what} yet")
+            use_cfg = ctx_uncond is not None and cfg_scale != 1.0
+            return self._denoise_windows(latent, [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], buf_tokens, scheduler, cfg_scale,
+                                         steps, on_step, round_bf16, sliding_window)
         res = self._tc_residuals() if tea_cache is not None else None
         if branch_exchange is not None:
             if (ctx_cond is None) == (ctx_uncond is None) or cfg_scale == 1.0:
@@ -1071,4 +1095,55 @@ class WanDiT:
                 on_step(i, latent)
         if self.sp_on:
             self.check_exchange()
+        return latent
+
+    # ------------------------------------------------------------------------------------
+    # Sliding temporal windows (sliding_window.py): per step, every window of the clip is a complete forward of its
+    # own on an engine prepared for the WINDOW's grid (RoPE from 0, attention inside the window) that patchifies the clip's latent
+    # at the window's frame offset; the windows' Euler updates are blended into a second latent.
+    def _window_engine(self, frames: int):
+        """The engine whose workspace fits a window of ``frames`` latent frames: this one, or a twin on the same weights (text K/V
+        caches are shared by reference) with a workspace of its own - one per distinct length, i.e. one for a shorter last window."""
+        if frames == self.grid.T:
+            return self
+        eng = self._win_engines.get(frames)
+        if eng is None:
+            eng = self._engine_copy()
+            eng.prepare(TokenGrid(4 * (frames - 1) + 1, self.grid.height, self.grid.width), graphs=self._graphs_on)
+            self._win_engines[frames] = eng
+        eng.cfg_batch, eng.share_stem, eng.native_forward = self.cfg_batch, self.share_stem, self.native_forward
+        return eng
+
+    def _denoise_windows(self, latent, ctxs, buf_tokens, scheduler, cfg_scale, steps, on_step, round_bf16, sw):
+        ops, per_frame = self.ops, self.grid.tokens_per_frame
+        C, T, H8, W8 = latent.shape
+        if T != sw.T or (H8, W8) != tuple(self.grid.latent_hw):
+            raise ValueError(f"sliding windows: latent {tuple(latent.shape)} does not match the plan ({sw.T} frames) / the prepared frame size {self.grid.latent_hw}")
+        if buf_tokens is not None and buf_tokens.shape[0] != T * per_frame:
+            raise ValueError(f"sliding windows: buf_tokens must cover the whole clip ({T * per_frame} rows: embed_buffers(whole_clip=True)), got {buf_tokens.shape[0]}")
+        coef = ops.to_device(torch.from_numpy(sw.coef), F32)          # ONE f32 table [windows, size] per call
+        engines = [self._window_engine(f1 - f0) for f0, f1 in sw.windows]
+        if self._win_next is None or self._win_next.shape != latent.shape:
+            self._win_next = ops.alloc(tuple(latent.shape), F32)
+        cur, nxt = latent, self._win_next
+        use_cfg = len(ctxs) == 2
+        try:
+            for i in (steps if steps is not None else range(len(scheduler.sigmas))):
+                ts = scheduler.timesteps[i]
+                nxt.copy_(cur)                                        # overlapping frames are read by two forwards of this step: not in place
+                for w, ((f0, f1), eng) in enumerate(zip(sw.windows, engines)):
+                    eng._lat_tok0 = f0 * per_frame
+                    bt = None if buf_tokens is None else buf_tokens[f0 * per_frame: f1 * per_frame]
+                    for _ in eng._computed_step(cur, ctxs, ts, bt, [eng.head_out[0], eng.head_out[1]]):
+                        pass
+                    ops.unpatchify_cfg_euler_window(nxt, eng.head_out[0], eng.head_out[1] if use_cfg else None, cfg_scale,
+                                                    scheduler.dsigma(i), coef[w], f0, 0, (f1 - f0) * per_frame, round_bf16=round_bf16)
+                cur, nxt = nxt, cur
+                if on_step is not None:
+                    on_step(i, cur)
+        finally:
+            for eng in engines:
+                eng._lat_tok0 = None
+        if cur is not latent:
+            latent.copy_(cur)                                         # the caller's tensor holds the result, as in the plain loop
         return latent

@@ -147,6 +147,9 @@ class WanVideoGenerator:
 
         print("Executing video generation...")
         if self._pool is not None:     # the N ranks behind this generator run the request; rank 0's frames come back
+            if getattr(self.pipe, "sliding_window_size", None) is not None or getattr(self.pipe, "sliding_window_stride", None) is not None:
+                raise ValueError("sliding_window_size / sliding_window_stride (ICV_SLIDING_WINDOW_SIZE / _STRIDE) cannot be combined with "
+                                 "ICV_WORLD > 1 (the worker pool's ranks shard ONE forward) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -372,6 +372,21 @@ class HipOps:
             latent.data_ptr(), native.ptr(vel_out), hc.data_ptr(), native.ptr(hu), hc.stride(0),
             cfg_scale, dsigma, C, T, H8, W8, tok0, n_tok, int(bool(round_bf16)), self._stream()), "icv_unpatchify_cfg_euler")
 
+    def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
+        """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
+        window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""
+        _chk(latent_next, F32, "euler_window.latent"); _chk(hc, F32, "euler_window.hc"); _chk(frame_coef, F32, "euler_window.frame_coef")
+        assert latent_next.is_contiguous() and frame_coef.is_contiguous()
+        C, T, H8, W8 = latent_next.shape
+        per_frame = (H8 // 2) * (W8 // 2)
+        if hc.shape[0] < n_tok or (hu is not None and (hu.shape[0] < n_tok or hu.stride(0) != hc.stride(0))):
+            raise ValueError("unpatchify_cfg_euler_window: head outputs have fewer rows than n_tok (or differ in row stride)")
+        if frame_coef.numel() * per_frame < tok0 + n_tok:
+            raise ValueError(f"unpatchify_cfg_euler_window: {frame_coef.numel()} frame coefficients do not cover window tokens [{tok0}, {tok0 + n_tok})")
+        native.check(self.lib.icv_unpatchify_cfg_euler_window(
+            latent_next.data_ptr(), hc.data_ptr(), native.ptr(hu), hc.stride(0), cfg_scale, dsigma, frame_coef.data_ptr(), frame0,
+            C, T, H8, W8, tok0, n_tok, int(bool(round_bf16)), self._stream()), "icv_unpatchify_cfg_euler_window")
+
     def cast_bf16(self, src, out):
         _chk(src, F32, "cast.src"); _chk(out, BF16, "cast.out")
         assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel()

@@ -274,6 +274,14 @@ class WanVideoPipeline:
         self.tea_cache_l1_thresh: Optional[float] = float(env_thresh) if env_thresh else None
         self.tea_cache_model_id = os.environ.get("ICV_TEACACHE_MODEL_ID", "")
         self.tea_cache_record: Optional[dict] = None
+        # Sliding temporal windows for clips longer than one trained forward (sliding_window.py; upstream DiffSynth's keywords of
+        # the same names, in LATENT frames).  Off by default; the caller of the unchanged WanVideoGenerator opts in with
+        # ICV_SLIDING_WINDOW_SIZE + ICV_SLIDING_WINDOW_STRIDE.  pipe.sliding_window_record: the last call's windows
+        # [(frame0, frame1), ...] (None when the call ran one forward per step and branch).
+        from . import sliding_window as _sw
+        self.sliding_window_size: Optional[int] = _sw.env_int(_sw.ENV_SIZE, os.environ.get(_sw.ENV_SIZE))
+        self.sliding_window_stride: Optional[int] = _sw.env_int(_sw.ENV_STRIDE, os.environ.get(_sw.ENV_STRIDE))
+        self.sliding_window_record: Optional[list] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -420,6 +428,13 @@ class WanVideoPipeline:
         teacache.coefficients(model_id)          # validate before any work is done
         return float(thresh), model_id
 
+    def _sliding_window_settings(self, size: Optional[int], stride: Optional[int]):
+        """(size, stride) in latent frames in effect for one call - each from the keyword, else the attribute (set from the
+        environment at construction) - validated; None = off."""
+        from . import sliding_window
+        return sliding_window.validate(self.sliding_window_size if size is None else size,
+                                       self.sliding_window_stride if stride is None else stride)
+
     # ---- D5: the generation call -----------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: str, negative_prompt: str = "", semantic_buffer_video=None,
@@ -428,16 +443,23 @@ class WanVideoPipeline:
                  cfg_scale: Optional[float] = None, sigma_shift: Optional[float] = None, rand_device: str = "cpu",
                  tile_size=(30, 52), tile_stride=(15, 26), progress_bar_cmd=None, return_latents: bool = False,
                  input_image=None, join_decode: bool = False, tea_cache_l1_thresh: Optional[float] = None,
-                 tea_cache_model_id: str = "", **unused):
+                 tea_cache_model_id: str = "", sliding_window_size: Optional[int] = None,
+                 sliding_window_stride: Optional[int] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
         cfg_scale = self.cfg_scale if cfg_scale is None else cfg_scale
         sigma_shift = self.sigma_shift if sigma_shift is None else sigma_shift
         grid = TokenGrid(num_frames, height, width)
-        engine = self._get_engine()
-        ops = engine.ops
-        tc_thresh, tc_id = self._tea_cache_settings(tea_cache_l1_thresh, tea_cache_model_id, engine.cfg)
+        # sliding temporal windows: settings and scope are checked before any GPU work (the engine packs the weights into HBM)
+        sw_plan = None
+        sw = self._sliding_window_settings(sliding_window_size, sliding_window_stride)
+        if sw is not None:
+            from . import sliding_window
+            sw_plan = sliding_window.plan(grid.T, *sw)
+            if len(sw_plan.windows) == 1:        # the clip fits one window: today's path, same launches, same bits
+                sw_plan = None
+        self.sliding_window_record = sw_plan.record() if sw_plan is not None else None
         world, rank = 1, 0
         from . import multigpu
         try:
@@ -446,6 +468,17 @@ class WanVideoPipeline:
                 world, rank = dist.get_world_size(), dist.get_rank()                        # left a dead group behind
         except Exception:  # pragma: no cover
             pass
+        if sw_plan is not None:
+            # first-version scope: each of these raises, none falls back to one full-length forward
+            tc_on = (self.tea_cache_l1_thresh if tea_cache_l1_thresh is None else tea_cache_l1_thresh) is not None
+            for on, what in ((world > 1, f"a process group of {world} ranks"),
+                             (self.dit.cfg.has_image_input, "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)"),
+                             (tc_on, "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call")):
+                if on:
+                    raise ValueError(f"sliding_window_size / sliding_window_stride cannot be combined with {what} yet")
+        engine = self._get_engine()
+        ops = engine.ops
+        tc_thresh, tc_id = self._tea_cache_settings(tea_cache_l1_thresh, tea_cache_model_id, engine.cfg)
         lkey = (world, rank, self.parallelism, cfg_scale != 1.0)
         # process groups are created once per (world, mode).  Behind a worker pool the cache belongs to the POOL, not to this
         # pipeline object: a second generator on the same pool gives rank 0 a new pipeline while the workers keep theirs, and
@@ -465,7 +498,11 @@ class WanVideoPipeline:
             if kv_exchange == "auto":
                 tune_key = (lkey, grid.S)
                 kv_exchange, sp_chunks = self._kv_tuned.get(tune_key, ("allgather", sp_chunks))
-        engine.prepare(grid, plan, group=layout.sp_group, sp_chunks=sp_chunks, kv_exchange=kv_exchange if layout.sp_world > 1 else None)
+        if sw_plan is not None:
+            # the workspace is a WINDOW's (every full-length window shares it; a shorter last one gets a second, dit._window_engine)
+            engine.prepare(TokenGrid(4 * (sw_plan.size - 1) + 1, height, width))
+        else:
+            engine.prepare(grid, plan, group=layout.sp_group, sp_chunks=sp_chunks, kv_exchange=kv_exchange if layout.sp_world > 1 else None)
         self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
         i2v = engine.cfg.has_image_input
@@ -515,7 +552,9 @@ class WanVideoPipeline:
             else:
                 lats = [self.vae.encode(_video_to_tensor(v, height, width), tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
                         for v in vids]
-            buf_tokens = engine.embed_buffers(torch.cat([x.to(torch.float32) for x in lats], dim=0))
+            # sliding windows: the buffers were VAE-encoded for the whole clip ONCE; their tokens too, a window reads a row range
+            buf_tokens = engine.embed_buffers(torch.cat([x.to(torch.float32) for x in lats], dim=0),
+                                              **(dict(whole_clip=True) if sw_plan is not None else {}))
         if i2v:
             y = self._image_cond_latents(input_image, grid, tiled, tile_size, tile_stride)
             buf_tokens = engine.embed_cond_latents(y, add_to=buf_tokens)
@@ -539,7 +578,7 @@ class WanVideoPipeline:
             it = progress_bar_cmd(it)
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
-                       round_bf16=self.reference_rounding, tea_cache=tc_plan)
+                       round_bf16=self.reference_rounding, tea_cache=tc_plan, **(dict(sliding_window=sw_plan) if sw_plan is not None else {}))
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
         # The DECODE is sharded (a collective of every rank: vae.TileShard broadcasts the tiles) only where every rank is known to
         # take part: behind a multigpu.WorkerPool (its workers pass join_decode=True) or when the caller says so
