@@ -299,7 +299,8 @@ int icv_instance_overlay_u8(const unsigned char* semantics_rgb, const int* insta
  * icv_depth_to_u16 replaces `(depth_np * 100).astype(np.uint16)`, the payload of every
  * `NNNNNN.voxel_depth_100.front.png` member of `voxel_depth_100_<res>_front.tar`
  * [R infinicube/inference/guidance_buffer_generation.py:668-672]: out[i] = (uint16)(int64)(depth[i] * scale),
- * one rounded f32 multiply, truncation toward zero, wrap modulo 2^16.  depth f32 [n] (16-byte aligned), out u16 [n]. */
+ * one rounded f32 multiply, truncation toward zero, wrap modulo 2^16.  depth f32 [n], out u16 [n]; any element
+ * alignment is accepted (16-byte aligned depth and 8-byte aligned out take the vector path). */
 int icv_depth_to_u16(const float* depth, int64_t n, float scale, unsigned short* out, void* stream);
 
 /* ---- the Wan-VAE's channel RMS norm (+ SiLU) as ONE pass over NDHWC rows ----------------------

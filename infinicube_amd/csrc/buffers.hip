@@ -322,20 +322,22 @@ extern "C" int icv_instance_overlay_u8(const unsigned char* semantics_rgb, const
 __global__ __launch_bounds__(256) void depth_to_u16_kernel(const float* __restrict__ depth, unsigned short* __restrict__ out,
                                                            float scale, int64_t n) {
   const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i + 3 < n) {
+  // a contiguous view may start anywhere in its allocation: unaligned pointers take the scalar path, like the kernels above
+  const bool vec = i + 3 < n && (((uintptr_t)depth & 15) | ((uintptr_t)out & 7)) == 0;
+  if (vec) {
     const float4 d = *reinterpret_cast<const float4*>(depth + i);
     ushort4 o;
     o.x = (unsigned short)(long long)__fmul_rn(d.x, scale); o.y = (unsigned short)(long long)__fmul_rn(d.y, scale);
     o.z = (unsigned short)(long long)__fmul_rn(d.z, scale); o.w = (unsigned short)(long long)__fmul_rn(d.w, scale);
     *reinterpret_cast<ushort4*>(out + i) = o;
   } else {
-    for (int64_t j = i; j < n; ++j) out[j] = (unsigned short)(long long)__fmul_rn(depth[j], scale);
+    const int64_t end = i + 4 < n ? i + 4 : n;
+    for (int64_t j = i; j < end; ++j) out[j] = (unsigned short)(long long)__fmul_rn(depth[j], scale);
   }
 }
 
 extern "C" int icv_depth_to_u16(const float* depth, int64_t n, float scale, unsigned short* out, void* stream) {
   ICV_REQUIRE(depth && out && n > 0, "icv_depth_to_u16: bad arguments");
-  ICV_REQUIRE(((uintptr_t)depth % 16 == 0) && ((uintptr_t)out % 8 == 0), "icv_depth_to_u16: buffers must be 16-byte / 8-byte aligned");
   const int64_t threads = (n + 3) / 4;
   hipLaunchKernelGGL(depth_to_u16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depth, out, scale, n);
   return icv_check_launch("icv_depth_to_u16");

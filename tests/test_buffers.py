@@ -1,7 +1,8 @@
 """SURVEY.md §8f row 1 — coordinate guidance buffer.  This oracle IS pinned: the golden arrays in
 tests/golden/coord_buffer_cases.npz are outputs of the reference's own function (generator:
 tests/golden/make_coord_buffer_golden.py).  CPU: oracle vs reference golden.  GPU: HIP path (C ABI) vs
-golden and vs the oracle at the full 93x480x832 size through size-independent properties."""
+golden and vs the oracle at the full 93x480x832 size through size-independent properties.
+Ragged widths, rows wider than a block, unaligned pointers and the other edges of these kernels: tests/test_buffer_edges_gpu.py."""
 import os
 
 import numpy as np
@@ -69,7 +70,8 @@ def test_hip_kernels_bit_exact_from_reference_host_values(name):
     # the valid mask and the gathered sample points are the reference's too (flattened order)
     mask = torch.empty((n * h * w,), dtype=torch.uint8, device="cuda:0")
     native.check(lib.icv_coord_valid_mask(depth.data_ptr(), kinv, tf.data_ptr(), n, h, w, mask.data_ptr(), st))
-    assert int(mask.sum()) == int((G[f"{name}_depth"] != 0).sum())
+    want_mask = B.coord_valid_mask_f32(G[f"{name}_depth"], G[f"{name}_kinv"], G[f"{name}_to_cam0"])
+    assert np.array_equal(mask.cpu().numpy().reshape(n, h, w), want_mask), "valid mask differs from the restatement's, pixel by pixel"
 
 
 @pytest.mark.gpu
