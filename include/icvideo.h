@@ -527,6 +527,17 @@ int icv_unpatchify_cfg_euler_window(float* latent_next, const float* hc, const f
                                     float dsigma, const float* frame_coef, int64_t frame0, int64_t C, int64_t T, int64_t H8,
                                     int64_t W8, int64_t tok0, int64_t n_tok, int round_bf16, void* stream);
 
+/* ---- LoRA merge into a packed projection weight ----------------------------------------------------------
+ * W bf16 [N, K] (row stride ldw elements >= K; may be a row range of a taller matrix), up bf16 [N, R] (lora_B / lora_up, ldu),
+ * down_t bf16 [K, R] (lora_A / lora_down TRANSPOSED, ldd):
+ *   W[n, k] <- bf16_rn( f32(W[n, k]) + alpha * sum_j up[n, j] * down_t[k, j] )
+ * The sum runs in f32 over the products of the bf16 operands (MFMA); alpha and the addition are one f32 fused multiply-add;
+ * ONE rounding, at the store.  In place: every holder of W's pointer sees the merged matrix.  Only the [N, K] elements are
+ * written.  Checked on the host before any launch: N % 64 == 0, K % 64 == 0, R % 32 == 0 and 32 <= R <= 512 (zero-pad smaller
+ * ranks: exact), the three pointers 16-byte aligned, the three row strides multiples of 8.  alpha == 0 launches nothing. */
+int icv_lora_merge_bf16(void* W, int64_t ldw, const void* up, int64_t ldu, const void* down_t, int64_t ldd, int64_t N, int64_t K,
+                        int64_t R, float alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,25 +159,26 @@ class WanDiT:
         for i in range(cfg.num_layers):
             p = f"blocks.{i}"
             sa, ca = f"{p}.self_attn", f"{p}.cross_attn"
+            M = lambda name, i=i: self._layer_matrix(sd, i, name)   # noqa: E731  packed projection (restore_lora repeats it)
             lw = dict(
-                wqkv=torch.cat([W(f"{sa}.q.weight"), W(f"{sa}.k.weight"), W(f"{sa}.v.weight")], 0).contiguous(),
+                wqkv=M("wqkv"),
                 bqkv=torch.cat([V(f"{sa}.q.bias"), V(f"{sa}.k.bias"), V(f"{sa}.v.bias")], 0).contiguous(),
                 nq=V(f"{sa}.norm_q.weight"), nk=V(f"{sa}.norm_k.weight") * self.k_fold,
-                wo=W(f"{sa}.o.weight"), bo=V(f"{sa}.o.bias"),
+                wo=M("wo"), bo=V(f"{sa}.o.bias"),
                 n3w=V(f"{p}.norm3.weight"), n3b=V(f"{p}.norm3.bias"),
-                xq_w=W(f"{ca}.q.weight"), xq_b=V(f"{ca}.q.bias"),
-                xkv_w=torch.cat([W(f"{ca}.k.weight"), W(f"{ca}.v.weight")], 0).contiguous(),
+                xq_w=M("xq_w"), xq_b=V(f"{ca}.q.bias"),
+                xkv_w=M("xkv_w"),
                 xkv_b=torch.cat([V(f"{ca}.k.bias"), V(f"{ca}.v.bias")], 0).contiguous(),
                 xnq=V(f"{ca}.norm_q.weight"), xnk=V(f"{ca}.norm_k.weight") * self.k_fold,
-                xo_w=W(f"{ca}.o.weight"), xo_b=V(f"{ca}.o.bias"),
-                f0_w=W(f"{p}.ffn.0.weight"), f0_b=V(f"{p}.ffn.0.bias"),
-                f2_w=W(f"{p}.ffn.2.weight"), f2_b=V(f"{p}.ffn.2.bias"),
+                xo_w=M("xo_w"), xo_b=V(f"{ca}.o.bias"),
+                f0_w=M("f0_w"), f0_b=V(f"{p}.ffn.0.bias"),
+                f2_w=M("f2_w"), f2_b=V(f"{p}.ffn.2.bias"),
             )
             if self.fp8:                                  # e4m3 rows + per-output-channel scale; bf16 copy dropped
                 for nm in self.fp8_set:
                     lw[nm] = self._quantize_weight(lw[nm])
             if cfg.has_image_input:
-                lw["xkv_img_w"] = torch.cat([W(f"{ca}.k_img.weight"), W(f"{ca}.v_img.weight")], 0).contiguous()
+                lw["xkv_img_w"] = M("xkv_img_w")
                 lw["xkv_img_b"] = torch.cat([V(f"{ca}.k_img.bias"), V(f"{ca}.v_img.bias")], 0).contiguous()
                 lw["xnk_img"] = V(f"{ca}.norm_k_img.weight") * self.k_fold
             self.layers.append(lw)
@@ -190,8 +191,49 @@ class WanDiT:
         # set by prepare(); here so that everything else reads them as plain attributes
         self.kv_gather, self.kv8, self.fp8_wire, self.attn_arrival, self.sp_err = None, None, False, False, None
         self._native, self._pair, self._twin = None, None, None
+        # LoRA adapters merged into the matrices above (apply_lora): [(adapter id, alpha)] in merge order, and which
+        # (weight name, layer) they touched - what restore_lora re-uploads
+        self.lora_applied, self.lora_touched = [], set()
 
     # ------------------------------------------------------------------------------------
+    # the state-dict linears behind each packed per-layer projection, in row order
+    LAYER_MATRICES = {"wqkv": ("self_attn.q", "self_attn.k", "self_attn.v"), "wo": ("self_attn.o",), "xq_w": ("cross_attn.q",),
+                      "xkv_w": ("cross_attn.k", "cross_attn.v"), "xo_w": ("cross_attn.o",), "f0_w": ("ffn.0",), "f2_w": ("ffn.2",),
+                      "xkv_img_w": ("cross_attn.k_img", "cross_attn.v_img")}
+
+    def _layer_matrix(self, sd, i: int, name: str) -> torch.Tensor:
+        """Layer ``i``'s projection ``name`` as the engine holds it: each linear rounded to bf16 on upload, rows concatenated."""
+        parts = [self.ops.to_device(sd[f"blocks.{i}.{lin}.weight"], BF16) for lin in self.LAYER_MATRICES[name]]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0).contiguous()
+
+    # ------------------------------------------------------------------------------------
+    # LoRA (lora.py, DESIGN.md §11).  Every projection is a plain row-major bf16 matrix that native contexts, the pair / window /
+    # twin engines and captured graphs hold BY POINTER, so W += alpha * B A in place reaches all of them: no rebuild, no re-bind,
+    # no re-capture.  What is derived from the weights per call (encode_context's cross-attention K / V) must be derived after
+    # the merge; the pipeline does.
+    def apply_lora(self, adapter, alpha: float = 1.0):
+        """Merge ``adapter`` (lora.Adapter) into the packed weights: one icv_lora_merge_bf16 launch per target linear, the
+        factors uploaded as bf16 (rounded once, as every matrix of this engine), one rounding of W per merge."""
+        plan = adapter.plan(self.cfg)
+        quantised = sorted({f"{e.name} (layer {e.layer})" for e in plan if isinstance(self.layers[e.layer][e.name], tuple)})
+        if quantised:      # checked for the whole adapter before the first launch: never a partial merge
+            raise ValueError("LoRA on an e4m3-quantised projection is outside the first-version scope (its bf16 copy was dropped at "
+                             f"load): {', '.join(quantised[:4])}; run that projection in bf16 (fp8_weights= / ICV_FP8_WEIGHTS) or merge offline")
+        for e in plan:
+            w = self.layers[e.layer][e.name][e.rows[0]: e.rows[1]]
+            self.ops.lora_merge(w, self.ops.to_device(e.up, BF16), self.ops.to_device(e.down_t, BF16), float(alpha) * e.scale)
+            self.lora_touched.add((e.name, e.layer))
+        self.lora_applied.append((adapter.id, float(alpha)))
+        return len(plan)
+
+    def restore_lora(self, state_dict: Dict[str, torch.Tensor]):
+        """Undo every merge: re-upload ONLY the touched matrices from ``state_dict`` into the EXISTING tensors (pointers stay
+        valid), packed as __init__ packs them - bit-identical to a freshly built engine."""
+        for name, layer in sorted(self.lora_touched):
+            self.layers[layer][name].copy_(self._layer_matrix(state_dict, layer, name))
+        self.lora_touched.clear()
+        del self.lora_applied[:]
+
     def _quantize_weight(self, w: torch.Tensor):
         q = torch.empty(w.shape, dtype=FP8, device=w.device)
         sc = torch.empty((w.shape[0],), dtype=F32, device=w.device)

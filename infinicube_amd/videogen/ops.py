@@ -412,3 +412,17 @@ class HipOps:
         assert out.is_contiguous() and out.numel() == n
         native.check(self.lib.icv_rel_l1_steps_f32(table.data_ptr(), n, cols, table.stride(0), out.data_ptr(),
                                                    self._stream()), "icv_rel_l1_steps_f32")
+
+    # ---- LoRA merge (lora.py) --------------------------------------------------------
+    def lora_merge(self, w, up, down_t, alpha: float):
+        """w += alpha * up @ down_t.T in place, one bf16 rounding: w bf16 [N, K] (a row range of a taller matrix is fine),
+        up bf16 [N, R], down_t bf16 [K, R]; shape / alignment contract of icv_lora_merge_bf16 (checked there, before any launch)."""
+        _chk(w, BF16, "lora_merge.w"); _chk(up, BF16, "lora_merge.up"); _chk(down_t, BF16, "lora_merge.down_t")
+        if w.dim() != 2 or up.dim() != 2 or down_t.dim() != 2:
+            raise ValueError("lora_merge: w, up and down_t must be matrices")
+        N, K = w.shape
+        R = up.shape[1]
+        if tuple(up.shape) != (N, R) or tuple(down_t.shape) != (K, R):
+            raise ValueError(f"lora_merge: w {tuple(w.shape)} needs up [N, R] and down_t [K, R], got {tuple(up.shape)} and {tuple(down_t.shape)}")
+        native.check(self.lib.icv_lora_merge_bf16(w.data_ptr(), w.stride(0), up.data_ptr(), up.stride(0), down_t.data_ptr(),
+                                                  down_t.stride(0), N, K, R, float(alpha), self._stream()), "icv_lora_merge_bf16")

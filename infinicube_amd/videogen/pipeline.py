@@ -282,6 +282,13 @@ class WanVideoPipeline:
         self.sliding_window_size: Optional[int] = _sw.env_int(_sw.ENV_SIZE, os.environ.get(_sw.ENV_SIZE))
         self.sliding_window_stride: Optional[int] = _sw.env_int(_sw.ENV_STRIDE, os.environ.get(_sw.ENV_STRIDE))
         self.sliding_window_record: Optional[list] = None
+        # LoRA adapters merged into the DiT's projection weights in HBM (lora.py; upstream DiffSynth's pipe.load_lora).  None by
+        # default; the caller of the unchanged WanVideoGenerator names files with ICV_LORA="pathA:0.8,pathB" (alpha defaults to 1),
+        # read here and loaded when the engine is first needed (the DiT they are validated against arrives after construction).
+        # pipe.lora_record: what is currently merged, [{path, alpha, matrices, rank}] (None when nothing is).
+        from . import lora as _lora
+        self.loras: List[dict] = [dict(path=p, alpha=a, adapter=None) for p, a in _lora.parse_env(os.environ.get(_lora.ENV))]
+        self.lora_record: Optional[list] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -330,6 +337,43 @@ class WanVideoPipeline:
         with no numeric effect."""
         self.vram_management_enabled = True
 
+    # ---- LoRA ----------------------------------------------------------------------------------
+    def load_lora(self, module, path, alpha: float = 1.0):
+        """Upstream's ``pipe.load_lora(pipe.dit, path, alpha=1)``: ``W += alpha * lora_B @ lora_A`` on the DiT's attention and FFN
+        linears.  Parses and validates the file against the DiT's shape now (host only); the merge into HBM happens when the
+        engine is next needed, adapters in the order they were loaded, one bf16 rounding each (dit.WanDiT.apply_lora)."""
+        from . import lora
+        if getattr(self, "remote", False):
+            raise RuntimeError(f"load_lora: this pipeline is the client of a multi-GPU worker pool and holds no weights; name the "
+                               f"adapter in {lora.ENV}=\"path:alpha,...\" before the generator is built (every rank merges into its own replica)")
+        if self.dit is None or module is not self.dit:
+            raise ValueError("load_lora: LoRA is supported on the DiT only - pass this pipeline's pipe.dit as the module")
+        adapter = lora.load_adapter(path)
+        adapter.plan(self.dit.cfg)                 # every shape / layer / target error surfaces here, before any GPU work
+        self.loras.append(dict(path=adapter.path, alpha=float(alpha), adapter=adapter))
+
+    def clear_lora(self):
+        """Forget every loaded adapter; the next call restores the touched matrices from the DiT's state dict."""
+        self.loras = []
+
+    def _reconcile_lora(self, engine):
+        """Make the engine's merged adapters equal ``self.loras``: merge what is missing when the merged ones are a prefix of the
+        wanted list, else restore the touched matrices and merge all.  Nothing wanted and nothing merged: no work at all."""
+        from . import lora
+        for e in self.loras:
+            if e["adapter"] is None:              # an ICV_LORA entry: loaded on first use
+                e["adapter"] = lora.load_adapter(e["path"])
+                e["adapter"].plan(self.dit.cfg)
+        wanted = [(e["adapter"].id, e["alpha"]) for e in self.loras]
+        done = len(engine.lora_applied)
+        if engine.lora_applied != wanted[:done]:
+            engine.restore_lora(self.dit.state_dict())
+            done = 0
+        for e in self.loras[done:]:
+            e["matrices"] = engine.apply_lora(e["adapter"], e["alpha"])
+        self.lora_record = [dict(path=e["path"], alpha=e["alpha"], matrices=e["matrices"], rank=e["adapter"].rank)
+                            for e in self.loras] or None
+
     # ---- engine ------------------------------------------------------------------------------
     def _get_ops(self):
         if self._ops is None:
@@ -363,6 +407,8 @@ class WanVideoPipeline:
                                   self.buffer_embedder.state_dict() if self.buffer_embedder else None,
                                   gemm_dtype=self.gemm_dtype, attn_dtype=self.attn_dtype)
             self._engine_key = key
+        if self.loras or self._engine.lora_applied:
+            self._reconcile_lora(self._engine)
         return self._engine
 
     def _autotune_kv(self, engine, latent, ctx, buf_tokens, ops):
