@@ -36,7 +36,8 @@ extern "C" {
  *    signature changed.
  * 5: icv_attention_fp8_fwd_pieces_gated (the e4m3 chunk launches gate on their pieces' arrival flags inside the kernel); no existing
  *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping);
- *    icv_unpatchify_cfg_euler_window (sliding temporal windows). */
+ *    icv_unpatchify_cfg_euler_window (sliding temporal windows); icv_lora_merge_bf16 (LoRA merge in HBM); icv_add_noise_f32
+ *    (video-to-video start latent). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -537,6 +538,16 @@ int icv_unpatchify_cfg_euler_window(float* latent_next, const float* hc, const f
  * ranks: exact), the three pointers 16-byte aligned, the three row strides multiples of 8.  alpha == 0 launches nothing. */
 int icv_lora_merge_bf16(void* W, int64_t ldw, const void* up, int64_t ldu, const void* down_t, int64_t ldd, int64_t N, int64_t K,
                         int64_t R, float alpha, void* stream);
+
+/* ---- video-to-video start latent --------------------------------------------------------------------------
+ * out[i] = (1 - sigma) * x0[i] + sigma * noise[i] over n f32 elements: the VAE-encoded input clip noised to the first sigma of a
+ * denoising_strength-shortened range.  1 - sigma is formed in f32; two products and one sum, no fused multiply-add (sigma == 1
+ * returns the noise for any finite x0, sigma == 0 returns x0).  round_bf16 != 0: both products and the sum are rounded to bf16
+ * (what a pipeline that keeps its latents in bf16 materialises); the caller rounds x0 and the noise themselves.
+ * out may be the same pointer as noise or as x0; any other overlap is the caller's error.  Any n and any 4-byte-aligned
+ * pointers: 16-byte vectors where the three pointers share their offset from a 16-byte boundary, element by element before and
+ * after that body and everywhere when the offsets differ.  n == 0 launches nothing; negative n or a null pointer is an error. */
+int icv_add_noise_f32(const float* x0, const float* noise, float* out, int64_t n, float sigma, int round_bf16, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,9 @@ class WanVideoGenerator:
             if getattr(self.pipe, "sliding_window_size", None) is not None or getattr(self.pipe, "sliding_window_stride", None) is not None:
                 raise ValueError("sliding_window_size / sliding_window_stride (ICV_SLIDING_WINDOW_SIZE / _STRIDE) cannot be combined with "
                                  "ICV_WORLD > 1 (the worker pool's ranks shard ONE forward) yet")
+            if getattr(self.pipe, "input_video", None) is not None or getattr(self.pipe, "denoising_strength", None) is not None:
+                raise ValueError("input_video / denoising_strength (ICV_INPUT_VIDEO / ICV_DENOISING_STRENGTH) cannot be combined with "
+                                 "ICV_WORLD > 1 (the start latent is noised in one process) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -426,3 +426,14 @@ class HipOps:
             raise ValueError(f"lora_merge: w {tuple(w.shape)} needs up [N, R] and down_t [K, R], got {tuple(up.shape)} and {tuple(down_t.shape)}")
         native.check(self.lib.icv_lora_merge_bf16(w.data_ptr(), w.stride(0), up.data_ptr(), up.stride(0), down_t.data_ptr(),
                                                   down_t.stride(0), N, K, R, float(alpha), self._stream()), "icv_lora_merge_bf16")
+
+    # ---- video-to-video start latent (v2v.py) ----------------------------------------
+    def add_noise(self, x0, noise, out, sigma: float, round_bf16=False):
+        """out = (1 - sigma) * x0 + sigma * noise, elementwise f32 (icv_add_noise_f32: no fused multiply-add; with round_bf16 both
+        products and the sum are rounded to bf16).  ``out`` may be ``noise`` or ``x0`` itself; any other overlap is the caller's error."""
+        _chk(x0, F32, "add_noise.x0"); _chk(noise, F32, "add_noise.noise"); _chk(out, F32, "add_noise.out")
+        if tuple(x0.shape) != tuple(noise.shape) or tuple(out.shape) != tuple(noise.shape):
+            raise ValueError(f"add_noise: x0 {tuple(x0.shape)}, noise {tuple(noise.shape)} and out {tuple(out.shape)} must have one shape")
+        assert x0.is_contiguous() and noise.is_contiguous() and out.is_contiguous()
+        native.check(self.lib.icv_add_noise_f32(x0.data_ptr(), noise.data_ptr(), out.data_ptr(), out.numel(), float(sigma),
+                                                int(bool(round_bf16)), self._stream()), "icv_add_noise_f32")

@@ -289,6 +289,14 @@ class WanVideoPipeline:
         from . import lora as _lora
         self.loras: List[dict] = [dict(path=p, alpha=a, adapter=None) for p, a in _lora.parse_env(os.environ.get(_lora.ENV))]
         self.lora_record: Optional[list] = None
+        # Video-to-video (v2v.py; upstream DiffSynth's keywords of the same names): start from the VAE-encoded input clip noised to
+        # the first sigma of a denoising_strength-shortened range.  Off by default; the caller of the unchanged WanVideoGenerator
+        # opts in with ICV_INPUT_VIDEO (a .npy of uint8 [N, H, W, 3] or a directory of images, read per call) +
+        # ICV_DENOISING_STRENGTH.  pipe.v2v_record: {"denoising_strength", "sigma_0"} of the last call (None when it started from noise).
+        from . import v2v as _v2v
+        self.input_video = os.environ.get(_v2v.ENV_VIDEO) or None
+        self.denoising_strength: Optional[float] = _v2v.env_strength(os.environ.get(_v2v.ENV_STRENGTH))
+        self.v2v_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -490,7 +498,8 @@ class WanVideoPipeline:
                  tile_size=(30, 52), tile_stride=(15, 26), progress_bar_cmd=None, return_latents: bool = False,
                  input_image=None, join_decode: bool = False, tea_cache_l1_thresh: Optional[float] = None,
                  tea_cache_model_id: str = "", sliding_window_size: Optional[int] = None,
-                 sliding_window_stride: Optional[int] = None, **unused):
+                 sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
+                 **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
@@ -506,6 +515,11 @@ class WanVideoPipeline:
             if len(sw_plan.windows) == 1:        # the clip fits one window: today's path, same launches, same bits
                 sw_plan = None
         self.sliding_window_record = sw_plan.record() if sw_plan is not None else None
+        # video-to-video: the clip is read (a path) and both settings are checked here, before any GPU work
+        from . import v2v
+        v2v_frames, strength = v2v.validate(self.input_video if input_video is None else input_video,
+                                            self.denoising_strength if denoising_strength is None else denoising_strength, num_frames)
+        self.v2v_record = None
         world, rank = 1, 0
         from . import multigpu
         try:
@@ -522,6 +536,8 @@ class WanVideoPipeline:
                              (tc_on, "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call")):
                 if on:
                     raise ValueError(f"sliding_window_size / sliding_window_stride cannot be combined with {what} yet")
+        if v2v_frames is not None and world > 1:
+            raise ValueError(f"input_video / denoising_strength cannot be combined with a process group of {world} ranks yet")
         engine = self._get_engine()
         ops = engine.ops
         tc_thresh, tc_id = self._tea_cache_settings(tea_cache_l1_thresh, tea_cache_model_id, engine.cfg)
@@ -549,7 +565,7 @@ class WanVideoPipeline:
             engine.prepare(TokenGrid(4 * (sw_plan.size - 1) + 1, height, width))
         else:
             engine.prepare(grid, plan, group=layout.sp_group, sp_chunks=sp_chunks, kv_exchange=kv_exchange if layout.sp_world > 1 else None)
-        self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding)
+        self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding, denoising_strength=strength)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
         i2v = engine.cfg.has_image_input
         clip_fea = None
@@ -586,21 +602,38 @@ class WanVideoPipeline:
         # multi-rank run: the VAE's tiles are dealt to ALL ranks of the job (vae.TileShard; bit-identical result on every rank)
         from .vae import TileShard
         vshard = dict(shard=TileShard.current()) if (world > 1 and getattr(self.vae, "supports_tile_shard", False)) else {}
+        vids = ()
         if self.buffer_embedder is not None and semantic_buffer_video is not None and coordinate_buffer_video is not None:
             vids = (semantic_buffer_video, coordinate_buffer_video)
             for vid in vids:
                 if len(vid) != num_frames:
                     raise ValueError(f"buffer video has {len(vid)} frames, num_frames={num_frames}")
-            if hasattr(self.vae, "encode_many"):      # both clips in one pass over their tiles, bytes normalised on the device
+        n_buf = len(vids)
+        if v2v_frames is not None:                    # the input clip rides in the buffers' pass (alone when there are none)
+            vids = vids + (v2v_frames,)
+        if vids:
+            if hasattr(self.vae, "encode_many"):      # the clips in one pass over their tiles, bytes normalised on the device
                 to_clip = _video_to_uint8 if getattr(self.vae, "accepts_uint8", False) else _video_to_tensor
                 lats = self.vae.encode_many([to_clip(v, height, width) for v in vids], tiled=tiled, tile_size=tile_size,
                                             tile_stride=tile_stride, **vshard)
             else:
                 lats = [self.vae.encode(_video_to_tensor(v, height, width), tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
                         for v in vids]
+        if n_buf:
             # sliding windows: the buffers were VAE-encoded for the whole clip ONCE; their tokens too, a window reads a row range
-            buf_tokens = engine.embed_buffers(torch.cat([x.to(torch.float32) for x in lats], dim=0),
+            buf_tokens = engine.embed_buffers(torch.cat([x.to(torch.float32) for x in lats[:n_buf]], dim=0),
                                               **(dict(whole_clip=True) if sw_plan is not None else {}))
+        if v2v_frames is not None:
+            # latent <- (1 - sigma_0) x0 + sigma_0 noise, once, on the device, into the noise's own tensor; sliding windows noise the
+            # whole clip's latent here, before the windowed loop.  reference_rounding: x0 through bf16 first, as the noise was.
+            x0 = lats[n_buf].to(torch.float32)
+            if tuple(x0.shape) != tuple(latent.shape):
+                raise ValueError(f"input_video encodes to a latent of shape {tuple(x0.shape)}, the call's latent is {tuple(latent.shape)}")
+            if self.reference_rounding:
+                x0 = x0.to(torch.bfloat16).to(torch.float32)
+            sigma_0 = self.scheduler.sigmas[0]
+            ops.add_noise(ops.to_device(x0, torch.float32), latent, latent, sigma_0, round_bf16=self.reference_rounding)
+            self.v2v_record = dict(denoising_strength=strength, sigma_0=sigma_0)
         if i2v:
             y = self._image_cond_latents(input_image, grid, tiled, tile_size, tile_stride)
             buf_tokens = engine.embed_cond_latents(y, add_to=buf_tokens)

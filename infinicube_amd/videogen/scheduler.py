@@ -34,14 +34,18 @@ def round_through_bf16(x: float) -> float:
 class FlowMatchScheduler:
     """``reference_rounding``: the timestep fed to the DiT is 1000 sigma rounded to bfloat16, as a pipeline that casts
     ``timestep.to(torch_dtype)`` before the sinusoidal embedding does ([EXT], ORACLE_RISKS.md R1); the sigmas of the
-    Euler update stay exact either way."""
+    Euler update stay exact either way.
+    ``denoising_strength`` s in (0, 1] (video-to-video): the SAME number of steps over the range that starts at
+    s instead of 1 - ``linspace(s, 0, N+1)[:-1]``, then the shift warp ([EXT], ORACLE_RISKS.md R22).  1.0 = the full range."""
 
-    def __init__(self, num_inference_steps: int = 50, shift: float = 5.0, reference_rounding: bool = False):
+    def __init__(self, num_inference_steps: int = 50, shift: float = 5.0, reference_rounding: bool = False,
+                 denoising_strength: float = 1.0):
         self.reference_rounding = reference_rounding
-        self.set_timesteps(num_inference_steps, shift)
+        self.set_timesteps(num_inference_steps, shift, denoising_strength)
 
-    def set_timesteps(self, num_inference_steps: int, shift: float = 5.0):
-        self.sigmas = flow_match_sigmas(num_inference_steps, shift)
+    def set_timesteps(self, num_inference_steps: int, shift: float = 5.0, denoising_strength: float = 1.0):
+        self.denoising_strength = denoising_strength
+        self.sigmas = flow_match_sigmas(num_inference_steps, shift, denoising_strength=denoising_strength)
         self.timesteps = [s * 1000.0 for s in self.sigmas]
         if self.reference_rounding:
             self.timesteps = [round_through_bf16(t) for t in self.timesteps]
