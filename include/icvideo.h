@@ -37,7 +37,7 @@ extern "C" {
  * 5: icv_attention_fp8_fwd_pieces_gated (the e4m3 chunk launches gate on their pieces' arrival flags inside the kernel); no existing
  *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping);
  *    icv_unpatchify_cfg_euler_window (sliding temporal windows); icv_lora_merge_bf16 (LoRA merge in HBM); icv_add_noise_f32
- *    (video-to-video start latent). */
+ *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -242,6 +242,19 @@ typedef struct icv_kv_piece {
 int icv_attention_fwd_pieces(const void* q, int64_t ldq, const icv_kv_piece* pieces, int64_t n_pieces, int64_t ldk, int64_t ldv,
                              void* o, int64_t ldo, int64_t Sq, int64_t heads, float scale, const uint32_t* flags, uint32_t* err,
                              int64_t timeout_us, void* trace, void* stream);
+/* Frame-windowed self-attention in ONE launch (csrc/attn7p.hip): q, k, v, o bf16 rows of frames * frame_rows tokens in
+ * (frame, row, column) order, so a latent frame is frame_rows contiguous rows.  A query of frame f attends to the keys of the frames g
+ * with |g - f| <= window or g < sink: in frames, lo = max(0, f - window), hi = min(frames, f + window + 1), and the key ranges are
+ *   sink == 0: [lo, hi);   sink > 0 and lo <= sink: [0, max(hi, sink));   otherwise [0, sink) then [lo, hi).
+ * Each work-group (head, frame, block of 256 rows of that frame) derives its ranges from these scalars and walks them as
+ * icv_attention_fwd_pieces walks pieces that are in place (same tiles, same order, ragged tail masked, softmax state in registers
+ * across the two ranges): frame f's rows are bit-identical to icv_attention_fwd_pieces on those rows with those pieces.  No arrival
+ * flags, no time-out, no error word.  window >= frames - 1 is dense attention.  Same leading-dimension rules as
+ * icv_attention_fwd_pieces; frames, frame_rows > 0; window, sink >= 0; sink <= frames; frames * frame_rows < 2^25.
+ * Replaces: one icv_attention_fwd_pieces launch per latent frame (each too small to fill the device); the reference attends densely. */
+int icv_attention_fwd_framewin(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                               void* o, int64_t ldo, int64_t frames, int64_t frame_rows, int64_t heads,
+                               int64_t window, int64_t sink, float scale, void* stream);
 /* flags[index] <- value with a system-scope release, enqueued on `stream` (one thread): the arrival flag of a piece whose rows were
  * delivered by something `stream` has waited for (an RCCL collective, a copy); delay_us > 0 first holds the stream for that long
  * (tests: a late peer). */

@@ -21,6 +21,13 @@
 //   * no cache maintenance is needed for the late rows: the rows of a piece are first read after its flag was seen, the launch's own
 //     acquire invalidated whatever an earlier launch left in L2 / L1, and pieces are whole rows (no cache line straddles two pieces),
 //     so no stale line of a piece can exist; the flag itself is polled with system-scope (uncached) loads.
+// FRAME-WINDOWED instantiation (attn7p_kernel<UNIT, true>, icv_attention_fwd_framewin): the same ring and tile, but every
+// work-group derives its OWN one or two pieces from the latent frame its query rows lie in.  Tokens are ordered (frame, row, column),
+// so a frame is F contiguous rows; a query of frame f reads the frames [f - window, f + window] plus the first `sink` frames: one or
+// two contiguous key ranges, computed from four scalars in the kernel arguments (no table in memory).  Work-groups are (head, frame,
+// block of 256 rows of that frame): a block never straddles a frame, rows past the frame's end are clamped for reads and never stored
+// - what happens at Sq in the other instantiations.  Pieces are always there (no flags, no time-out, no error word): the ring runs
+// through the boundary between the two pieces as it does for a piece with flag < 0.
 // Replaces: the chunked icv_attention_fwd_chunk sequence of the sequence-parallel self-attention (the fork's / xDiT-USP's gather-then-
 // flash_attention [EXT]); the reference itself has no such path (one GPU, [R infinicube/inference/guidance_buffer_generation.py:759-766]).
 #include "attn_common.h"
@@ -54,6 +61,9 @@ struct Params {
   unsigned long long* ptrace;          // diagnostics: [work-group][piece] tick at which the piece's first tile was started
   int n_pieces;
   Piece piece[MAX_PIECES];
+  // frame-windowed instantiation only (keys / values: a.k, a.v; a.Sq = frames * frame_rows); behind the pieces, so that nothing the
+  // other instantiations read moves
+  int fw_frames, fw_frame_rows, fw_window, fw_sink;
 };
 
 __device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst) {
@@ -89,7 +99,8 @@ __device__ __forceinline__ unsigned load_flag_async(const unsigned* f) {
   return v;
 }
 
-template <bool UNIT>
+// FW: the frame-windowed instantiation (see the head of this file)
+template <bool UNIT, bool FW = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7p_kernel(Params pp) {
   const attc::Params& p = pp.a;
   const float p_lim = __builtin_amdgcn_exp2f(p.thr);
@@ -103,11 +114,35 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   int head, qb;
   attc::work_item(p, head, qb);
-  const int64_t q0 = (int64_t)qb * QB + wave * 32;
+  int64_t q0 = (int64_t)qb * QB + wave * 32;
+  int64_t q_end = 0;                    // FW: first row this work-group may neither read as a query nor store (the others: p.Sq)
+  // FW: this work-group's pieces, in frames [fw_a, fw_b) (wave-uniform scalars), and how many of them.  They derive from blockIdx and
+  // kernel arguments ONLY, so they - and P_ROWS / skv_d / nt_d, the loop bounds made of them - live in SGPRs without a readfirstlane;
+  // mix in nothing per-lane (tid, lane, a loaded value) or those bounds turn into VGPR values and the loops into divergent ones.
+  int fw_np = 1, fw_a0 = 0, fw_b0 = 0, fw_a1 = 0, fw_b1 = 0;
+  if constexpr (FW) {
+    const int T = pp.fw_frames, F = pp.fw_frame_rows, W = pp.fw_window, sink = pp.fw_sink;
+    const int bpf = (F + QB - 1) / QB;  // q-blocks per frame
+    const int f = qb / bpf;
+    q0 = (int64_t)f * F + (qb - f * bpf) * QB + wave * 32;
+    q_end = (int64_t)(f + 1) * F;
+    const int lo = f - W > 0 ? f - W : 0;
+    const int hi = f + W + 1 < T ? f + W + 1 : T;
+    if (sink == 0) {
+      fw_a0 = lo; fw_b0 = hi;
+    } else if (lo <= sink) {            // the window touches or overlaps the sink: one piece
+      fw_a0 = 0; fw_b0 = hi > sink ? hi : sink;
+    } else {
+      fw_np = 2;
+      fw_a0 = 0; fw_b0 = sink;
+      fw_a1 = lo; fw_b1 = hi;
+    }
+  }
   const unsigned long long t_start = p.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
   const bf16_t* qh = p.q + (int64_t)head * D;
   int64_t qr_c = q0 + l31;
-  qr_c = qr_c < p.Sq ? qr_c : p.Sq - 1;
+  if constexpr (FW) qr_c = qr_c < q_end ? qr_c : q_end - 1;
+  else qr_c = qr_c < p.Sq ? qr_c : p.Sq - 1;
 
   // ---- softmax state (registers, across all pieces) ----
   f32x16 ot[4];
@@ -145,12 +180,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   const bf16_t* kh_d = nullptr;
   const bf16_t* vh_d = nullptr;
   int skv_d = 0, nt_d = 0;
+#define P_ROWS(J_) (FW ? ((J_) ? fw_b1 - fw_a1 : fw_b0 - fw_a0) * pp.fw_frame_rows : __builtin_amdgcn_readfirstlane(pp.piece[FW ? 0 : (J_)].rows))
 #define P_SET_DMA_PIECE(J_)                                              \
   {                                                                      \
-    const Piece& pc_ = pp.piece[(J_)];                                   \
-    kh_d = pc_.k + (int64_t)head * D;                                    \
-    vh_d = pc_.v + (int64_t)head * D;                                    \
-    skv_d = __builtin_amdgcn_readfirstlane(pc_.rows);                    \
+    if constexpr (FW) {                                                  \
+      const int64_t r0_ = (int64_t)((J_) ? fw_a1 : fw_a0) * pp.fw_frame_rows; \
+      kh_d = p.k + r0_ * p.ldk + (int64_t)head * D;                      \
+      vh_d = p.v + r0_ * p.ldv + (int64_t)head * D;                      \
+      skv_d = P_ROWS(J_);                                                \
+    } else {                                                             \
+      const Piece& pc_ = pp.piece[(J_)];                                 \
+      kh_d = pc_.k + (int64_t)head * D;                                  \
+      vh_d = pc_.v + (int64_t)head * D;                                  \
+      skv_d = __builtin_amdgcn_readfirstlane(pc_.rows);                  \
+    }                                                                    \
     nt_d = (skv_d + KVB - 1) / KVB;                                      \
   }
   // tile T_ of the DMA piece (clamped to its last tile: a request past the end re-reads that tile into a dead stage) -> ring stage STG_
@@ -181,7 +224,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   } while (0)
   // blocking wait for piece J_ (a bubble): ONE lane polls, everybody else parks at the barrier; bounded by the time-out
 #define P_WAIT_PIECE(J_)                                                                                          \
-  {                                                                                                               \
+  if constexpr (!FW) {                                                                                            \
     const int fi_ = __builtin_amdgcn_readfirstlane(pp.piece[(J_)].flag);                                          \
     if (fi_ >= 0) {                                                                                               \
       if (tid == 0) {                                                                                             \
@@ -302,7 +345,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   };
 
   // ---- walk the pieces ----
-  const int np = __builtin_amdgcn_readfirstlane(pp.n_pieces);
+  const int np = FW ? fw_np : __builtin_amdgcn_readfirstlane(pp.n_pieces);
   unsigned gt = 0;                 // ring position of the current piece's tile 0 (always even)
   unsigned iv = 0;                 // interval counter (verdict word parity)
   P_WAIT_PIECE(0);
@@ -312,15 +355,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   P_BARRIER();
   for (int pj = 0; pj < np; ++pj) {
-    const int skv = __builtin_amdgcn_readfirstlane(pp.piece[pj].rows);
+    const int skv = P_ROWS(pj);
     const int nt = (skv + KVB - 1) / KVB;
     const unsigned g_next = gt + (unsigned)((nt + 1) & ~1);
     const bool has_next = pj + 1 < np;
-    const int nflag = has_next ? __builtin_amdgcn_readfirstlane(pp.piece[has_next ? pj + 1 : pj].flag) : -1;
-    const unsigned nvalue = has_next ? pp.piece[has_next ? pj + 1 : pj].value : 0u;
+    const int nflag = has_next && !FW ? __builtin_amdgcn_readfirstlane(pp.piece[has_next ? pj + 1 : pj].flag) : -1;
+    const unsigned nvalue = has_next && !FW ? pp.piece[has_next ? pj + 1 : pj].value : 0u;
     bool next_ready = has_next && nflag < 0;      // wave-uniform
     bool next_issued = false;
-    if (pp.ptrace && tid == 0) pp.ptrace[(size_t)blockIdx.x * np + pj] = __builtin_amdgcn_s_memrealtime();
+    if (!FW && pp.ptrace && tid == 0) pp.ptrace[(size_t)blockIdx.x * np + pj] = __builtin_amdgcn_s_memrealtime();
     for (int t = 0; t < nt; t += 2) {
       const bool last_iv = t + 2 >= nt;
       if (!last_iv) {                                    // the other half of the ring: last read in the previous interval
@@ -356,7 +399,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  attc::store_result(p, q0 + l31, head, hi, ot, m_run, l_run);
+  // FW: a row past the frame's end belongs to the next frame's work-group - hand store_result a row it does not store
+  attc::store_result(p, !FW || q0 + l31 < q_end ? q0 + l31 : p.Sq, head, hi, ot, m_run, l_run);
   if (p.trace && tid == 0 && (int)blockIdx.x < p.trace_cap) {
     unsigned hwid, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -364,19 +408,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     unsigned long long* t = p.trace + (size_t)blockIdx.x * 4;
     t[0] = t_start; t[1] = __builtin_amdgcn_s_memrealtime(); t[2] = hwid; t[3] = xcc;
   }
+#undef P_ROWS
 #undef P_SET_DMA_PIECE
 #undef P_DMA_TILE
 #undef P_BARRIER
 #undef P_WAIT_PIECE
 }
 
-template <bool UNIT>
+template <bool UNIT, bool FW = false>
 int launch(const Params& pp, hipStream_t st) {
   static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT>, LDS_BYTES, &attr_set, "attn7p")) return rc;
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW>, LDS_BYTES, &attr_set, "attn7p")) return rc;
   const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
-  hipLaunchKernelGGL((attn7p_kernel<UNIT>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
-  return icv_check_launch("icv_attention_fwd_pieces");
+  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
+  return icv_check_launch(FW ? "icv_attention_fwd_framewin" : "icv_attention_fwd_pieces");
 }
 
 }  // namespace att7p
@@ -430,6 +475,35 @@ int icv_attn7p_single(const void* q, int64_t ldq, const void* k, int64_t ldk, co
   att7p::Piece& d = pp.piece[0];
   d.k = (const bf16_t*)k; d.v = (const bf16_t*)v; d.rows = (int)Skv; d.flag = -1; d.value = 0; d.pad = 0;
   return (pp.a.sc == 1.0f && icv_get_option_int("attn_unit_scale", 1)) ? att7p::launch<true>(pp, st) : att7p::launch<false>(pp, st);
+}
+
+// Frame-windowed self-attention in ONE launch (see the head of this file and include/icvideo.h)
+extern "C" int icv_attention_fwd_framewin(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
+                                          int64_t frames, int64_t frame_rows, int64_t heads, int64_t window, int64_t sink, float scale, void* stream) {
+  ICV_REQUIRE(q && k && v && o, "icv_attention_fwd_framewin: null pointer");
+  ICV_REQUIRE(frames > 0 && frame_rows > 0 && heads > 0, "icv_attention_fwd_framewin: empty problem (frames=%lld frame_rows=%lld heads=%lld)",
+              (long long)frames, (long long)frame_rows, (long long)heads);
+  ICV_REQUIRE(window >= 0 && sink >= 0, "icv_attention_fwd_framewin: window (%lld) and sink (%lld) must be >= 0", (long long)window, (long long)sink);
+  ICV_REQUIRE(sink <= frames, "icv_attention_fwd_framewin: sink (%lld) exceeds the %lld frames", (long long)sink, (long long)frames);
+  ICV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "icv_attention_fwd_framewin: leading dims must keep 16-byte row alignment");
+  // a piece is at most every row; the LDS-DMA addresses keep 32-bit per-lane byte offsets from a tile base: a tile spans 64 rows
+  ICV_REQUIRE(frames < (1LL << 31) / 64 && frame_rows < (1LL << 31) / 64 && frames * frame_rows < (1LL << 31) / 64,
+              "icv_attention_fwd_framewin: %lld frames of %lld rows: key axis too large", (long long)frames, (long long)frame_rows);
+  ICV_REQUIRE(64 * ldk * 2 < (1LL << 32) && 64 * ldv * 2 < (1LL << 32), "icv_attention_fwd_framewin: row stride too large");
+  const int64_t nqb = frames * ((frame_rows + att7p::QB - 1) / att7p::QB);
+  ICV_REQUIRE(heads * nqb < (1LL << 31), "icv_attention_fwd_framewin: %lld work-groups", (long long)(heads * nqb));
+  att7p::Params pp;
+  attc::fill_params(pp.a, q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, nullptr, 0, 0, frames * frame_rows, frames * frame_rows, heads, scale, 256);
+  pp.a.nqb = (int)nqb;                 // q-blocks never straddle a frame
+  pp.a.trace = icv_attention_trace_buffer(&pp.a.trace_cap);
+  pp.flags = nullptr; pp.err = nullptr; pp.timeout_ticks = 0; pp.ptrace = nullptr;
+  pp.n_pieces = 0;
+  pp.fw_frames = (int)frames;
+  pp.fw_frame_rows = (int)frame_rows;
+  pp.fw_window = (int)(window < frames ? window : frames);      // beyond frames - 1 every range is [0, frames)
+  pp.fw_sink = (int)sink;
+  hipStream_t st = (hipStream_t)stream;
+  return (pp.a.sc == 1.0f && icv_get_option_int("attn_unit_scale", 1)) ? att7p::launch<true, true>(pp, st) : att7p::launch<false, true>(pp, st);
 }
 
 namespace {

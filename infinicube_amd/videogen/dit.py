@@ -590,6 +590,32 @@ class WanDiT:
             except Exception:  # pragma: no cover - interpreter shutdown
                 pass
 
+    # Frame-windowed self-attention (attn_window.py).  None = dense.  The setting lives on the engine that was prepared;
+    # the 2n-row pair engine reads it from there (_blocks), the dual-stream twin is handed it per step.
+    attn_window = None
+
+    def set_attention_window(self, window=None, sink=None):
+        """Self-attention of every layer reads, per query, only the latent frames within ``window`` of the query's own plus the first
+        ``sink`` frames (ONE icv_attention_fwd_framewin launch per layer and branch).  None = dense attention (the default)."""
+        from . import attn_window
+        self.attn_window = attn_window.validate(window, sink)
+        self._framewin()                                   # a combination that is out of scope raises here when the grid is known
+        return self
+
+    def _framewin(self):
+        """(window, sink) when the prepared grid's self-attention runs frame-windowed; None when the setting is off or the window
+        covers the whole clip (every range is [0, T): the plain launch, same bits as without the setting)."""
+        from . import attn_window
+        aw = self.attn_window
+        grid = getattr(self, "grid", None)
+        if aw is None or grid is None or attn_window.dense(grid.T, aw[0]):
+            return None
+        if self.sp_on:
+            raise ValueError("attention_window_frames cannot be combined with sequence parallelism (world > 1) yet")
+        if self.attn_fp8:
+            raise ValueError("attention_window_frames cannot be combined with the e4m3 self-attention mode (attn_dtype='fp8') yet")
+        return aw[0], min(aw[1], grid.T)
+
     def _native_eligible(self) -> bool:
         # the C driver knows the RCCL transport, bf16 rows on the wire and the chunked carried-state launches - nothing newer: with e4m3
         # on the wire, the copy-engine transport or the arrival-driven attention the per-op driver runs (ADVICE r5: it used to take
@@ -597,7 +623,9 @@ class WanDiT:
         sp_ok = not self.sp_on or (isinstance(self.kv_gather, KVGather) and self.kv_gather.mode != "ipc"
                                    and not self.fp8_wire and not self.attn_arrival)
         # ... and it patchifies from token 0 of the latent: a sliding window starts at a frame offset, so the per-op driver runs
-        return self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok and self._lat_tok0 is None
+        # ... and its self-attention is dense (the frame-windowed launch is driven per op)
+        return (self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok and self._lat_tok0 is None
+                and self._framewin() is None)
 
     def native_profile(self, enable: bool):
         """Time every self-attention launch of the native forward with HIP events on the launch stream (bench.py)."""
@@ -837,7 +865,9 @@ class WanDiT:
             stem = None
         if self._graphs_on:
             # a window's offset into the latent is an argument of the captured patchify: part of the key
-            key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem, self._lat_tok0)
+            # ... and so is the attention window: another launch with other scalars
+            key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem, self._lat_tok0,
+                   self._framewin())
             entry = self._graphs.get(key)
             if entry is None:
                 # first call with these buffers: run eagerly (that IS this call's result; it also lets every kernel do
@@ -910,6 +940,7 @@ class WanDiT:
         d, H, eps, scale = cfg.dim, cfg.num_heads, cfg.eps, self.attn_scale      # scale = ln 2: K already carries (1/sqrt(hd)) * log2(e)
         q, k, v = t.qkv[0], t.qkv[1], t.qkv[2]
         views = [(b, q[b.rows], k[b.rows], v[b.rows], t.att[b.rows]) for b in branches]      # once per forward, not per layer
+        fw = self._framewin()                                # frame-windowed self-attention: (window, sink) | None
         for i in range(L):
             lw = self.layers[i]
             m = self.mod[i]
@@ -945,7 +976,9 @@ class WanDiT:
                             t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv[j][rs], EPI_BF16, rows=slice(j * d, (j + 1) * d))
                     for _, qb, kb, vb, ab in active:
                         ops.rmsnorm_rope(qb, lw["nq"], kb, lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)  # K5
-                        if self.attn8_ws is not None:
+                        if fw is not None:
+                            ops.attention_framewin(qb, kb, vb, ab, H, scale, self.grid.T, self.grid.tokens_per_frame, *fw)   # K6 (windowed)
+                        elif self.attn8_ws is not None:
                             ops.attention_fp8(qb, kb, vb, ab, H, self.attn8_ws)                               # K6 (e4m3)
                         else:
                             ops.attention(qb, kb, vb, ab, H, scale)                                           # K6
@@ -1064,7 +1097,7 @@ class WanDiT:
             # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
             # filled by the other branch's kernels
             twin, side = self._cfg_twin()
-            twin._lat_tok0 = self._lat_tok0
+            twin._lat_tok0, twin.attn_window = self._lat_tok0, self.attn_window
             main = torch.cuda.current_stream(self.ops.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -1100,6 +1133,8 @@ class WanDiT:
         the forwards on each temporal window and blends their updates (_denoise_windows); this engine must be prepared for a
         window's grid, ``buf_tokens`` are the whole clip's (embed_buffers(whole_clip=True)).  None or ONE window: this loop."""
         ops, plan = self.ops, self.plan
+        if sliding_window is not None and len(sliding_window.windows) > 1 and self._framewin() is not None:
+            raise ValueError("attention_window_frames cannot be combined with sliding_window_size in the same call yet")
         if sliding_window is not None and len(sliding_window.windows) > 1:
             for on, what in ((self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)"),
                              (self.cond_w is not None, "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)"),

@@ -351,6 +351,19 @@ class HipOps:
             q.data_ptr(), q.stride(0), ctypes.cast(arr, ctypes.c_void_p), len(pieces), ldk or 0, ldv or 0, o.data_ptr(), o.stride(0), q.shape[0], heads, scale,
             native.ptr(flags), native.ptr(err), int(timeout_us), native.ptr(trace), self._stream()), "icv_attention_fwd_pieces")
 
+    def attention_framewin(self, q, k, v, o, heads: int, scale: float, frames: int, frame_rows: int, window: int, sink: int):
+        """K6, frame-windowed (csrc/attn7p.hip): ONE launch in which the queries of latent frame f (``frame_rows``
+        contiguous rows) read the keys of the frames within ``window`` of f plus the first ``sink`` frames."""
+        for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+            _chk(t, BF16, f"attention_framewin.{nm}")
+        rows = frames * frame_rows
+        if not (q.shape[0] == k.shape[0] == v.shape[0] == rows and o.shape[0] >= rows):
+            raise ValueError(f"attention_framewin: {frames} frames of {frame_rows} rows, but q / k / v / o have "
+                             f"{q.shape[0]} / {k.shape[0]} / {v.shape[0]} / {o.shape[0]} rows")
+        native.check(self.lib.icv_attention_fwd_framewin(
+            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), o.data_ptr(), o.stride(0),
+            frames, frame_rows, heads, window, sink, scale, self._stream()), "icv_attention_fwd_framewin")
+
     def flag_write(self, flags, index: int, value: int, delay_us: int = 0, stream: Optional[int] = None):
         """flags[index] <- value (system-scope release) on ``stream`` (default: the current one), optionally after holding it delay_us."""
         assert flags.dtype in (torch.int32, torch.uint32) and flags.is_contiguous()

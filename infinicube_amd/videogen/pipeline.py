@@ -297,6 +297,14 @@ class WanVideoPipeline:
         self.input_video = os.environ.get(_v2v.ENV_VIDEO) or None
         self.denoising_strength: Optional[float] = _v2v.env_strength(os.environ.get(_v2v.ENV_STRENGTH))
         self.v2v_record: Optional[dict] = None
+        # Frame-windowed self-attention (attn_window.py): every query reads the latent frames within
+        # attention_window_frames of its own plus the first attention_sink_frames frames.  Off by default; the caller of the unchanged
+        # WanVideoGenerator opts in with ICV_ATTN_WINDOW_FRAMES (+ ICV_ATTN_SINK_FRAMES).  pipe.attention_window_record:
+        # {"window", "sink", "key_fraction"} of the last call (None when its attention was dense).
+        from . import attn_window as _aw
+        self.attention_window_frames: Optional[int] = _aw.env_int(_aw.ENV_WINDOW, os.environ.get(_aw.ENV_WINDOW))
+        self.attention_sink_frames: Optional[int] = _aw.env_int(_aw.ENV_SINK, os.environ.get(_aw.ENV_SINK))
+        self.attention_window_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -489,6 +497,14 @@ class WanVideoPipeline:
         return sliding_window.validate(self.sliding_window_size if size is None else size,
                                        self.sliding_window_stride if stride is None else stride)
 
+    def _attention_window_settings(self, window: Optional[int], sink: Optional[int], T: int):
+        """(window, sink) in latent frames in effect for one call of T latent frames - each from the keyword, else the attribute (set
+        from the environment at construction) - validated; None = dense attention (off, or a window that covers the clip)."""
+        from . import attn_window
+        aw = attn_window.validate(self.attention_window_frames if window is None else window,
+                                  self.attention_sink_frames if sink is None else sink, T)
+        return None if aw is None or attn_window.dense(T, aw[0]) else aw
+
     # ---- D5: the generation call -----------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: str, negative_prompt: str = "", semantic_buffer_video=None,
@@ -499,6 +515,7 @@ class WanVideoPipeline:
                  input_image=None, join_decode: bool = False, tea_cache_l1_thresh: Optional[float] = None,
                  tea_cache_model_id: str = "", sliding_window_size: Optional[int] = None,
                  sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
+                 attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
                  **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
@@ -515,6 +532,14 @@ class WanVideoPipeline:
             if len(sw_plan.windows) == 1:        # the clip fits one window: today's path, same launches, same bits
                 sw_plan = None
         self.sliding_window_record = sw_plan.record() if sw_plan is not None else None
+        # frame-windowed self-attention: validated here too; a window that covers the clip is today's path, same launches, same bits
+        aw = self._attention_window_settings(attention_window_frames, attention_sink_frames, grid.T)
+        if aw is not None and sw_plan is not None:         # more than one window, as the engine's own check (WanDiT.denoise) has it
+            raise ValueError("attention_window_frames / attention_sink_frames cannot be combined with sliding_window_size in the same call yet")
+        if aw is not None and self.attn_dtype == "fp8":
+            raise ValueError("attention_window_frames / attention_sink_frames cannot be combined with the e4m3 self-attention mode "
+                             "(torch_dtype=float8_e4m3fn) yet")
+        self.attention_window_record = None
         # video-to-video: the clip is read (a path) and both settings are checked here, before any GPU work
         from . import v2v
         v2v_frames, strength = v2v.validate(self.input_video if input_video is None else input_video,
@@ -536,6 +561,8 @@ class WanVideoPipeline:
                              (tc_on, "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call")):
                 if on:
                     raise ValueError(f"sliding_window_size / sliding_window_stride cannot be combined with {what} yet")
+        if aw is not None and world > 1:
+            raise ValueError(f"attention_window_frames / attention_sink_frames cannot be combined with a process group of {world} ranks yet")
         if v2v_frames is not None and world > 1:
             raise ValueError(f"input_video / denoising_strength cannot be combined with a process group of {world} ranks yet")
         engine = self._get_engine()
@@ -565,6 +592,11 @@ class WanVideoPipeline:
             engine.prepare(TokenGrid(4 * (sw_plan.size - 1) + 1, height, width))
         else:
             engine.prepare(grid, plan, group=layout.sp_group, sp_chunks=sp_chunks, kv_exchange=kv_exchange if layout.sp_world > 1 else None)
+        if aw is not None or engine.attn_window is not None:
+            engine.set_attention_window(*(aw or (None, None)))
+        if aw is not None:
+            from . import attn_window
+            self.attention_window_record = attn_window.record(grid.T, *aw)
         self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding, denoising_strength=strength)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
         i2v = engine.cfg.has_image_input
