@@ -37,7 +37,8 @@ extern "C" {
  * 5: icv_attention_fp8_fwd_pieces_gated (the e4m3 chunk launches gate on their pieces' arrival flags inside the kernel); no existing
  *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping);
  *    icv_unpatchify_cfg_euler_window (sliding temporal windows); icv_lora_merge_bf16 (LoRA merge in HBM); icv_add_noise_f32
- *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch). */
+ *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch);
+ *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -276,6 +277,22 @@ int icv_patchify(const float* latent, int64_t C, int64_t T, int64_t H8, int64_t 
 int icv_unpatchify_cfg_euler(float* latent, float* vel_out, const float* hc, const float* hu,
                              int64_t ldh, float cfg_scale, float dsigma, int64_t C, int64_t T,
                              int64_t H8, int64_t W8, int64_t tok0, int64_t n_tok, int round_bf16, void* stream);
+
+/* ---- multistep samplers: unpatchify + CFG combine + a linear multistep update, fused ----
+ * The counterpart of icv_unpatchify_cfg_euler for a solver that keeps a history of x0-predictions (UniPC).  Token handling, the
+ * head-output layout and the velocity v (round_bf16 included) are that entry's; the solver arithmetic is always f32, evaluated
+ * left to right without fused multiply-adds.  Per latent element of the local tokens r in [0, n_tok), in one pass:
+ *     m      = x - sigma * v                                              -> m_new
+ *     x_c    = a0 * x_hat + a1 * m_prev + a2 * m_prev2 + a3 * m           -> x_hat      (corrector == 0: x_c = x, a0..a3 must be 0)
+ *     x_next = c0 * x_c + c1 * m + c2 * m_prev                            -> latent, in place
+ * latent, x_hat, m_new, m_prev, m_prev2: f32 [C, T, H8, W8], five different buffers (the host rotates the three x0-prediction
+ * slots through the roles new / previous / one before).  m_prev / m_prev2 may be NULL when their coefficients are 0; a buffer
+ * whose coefficient is 0 is not read.  Elements of tokens outside [tok0, tok0 + n_tok) are not touched in any buffer.
+ * Every argument check runs on the host before the launch. */
+int icv_unpatchify_cfg_multistep(float* latent, float* x_hat, float* m_new, const float* m_prev, const float* m_prev2,
+                                 const float* hc, const float* hu, int64_t ldh, float cfg_scale, float sigma, int corrector,
+                                 float a0, float a1, float a2, float a3, float c0, float c1, float c2, int64_t C, int64_t T,
+                                 int64_t H8, int64_t W8, int64_t tok0, int64_t n_tok, int round_bf16, void* stream);
 
 /* ---- coordinate guidance buffer (producer of the hot path's input) ---------------
  * Replaces `generate_coordinate_buffer_from_memory_global_norm` [R infinicube/utils/buffer_utils.py:180-265]

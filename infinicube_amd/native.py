@@ -112,6 +112,8 @@ SIGNATURES.update({
     "icv_unpatchify_cfg_euler_window": (c_int, [_P, _P, _P, _I, _F, _F, _P, _I, _I, _I, _I, _I, _I, _I, c_int, _P]),
     "icv_lora_merge_bf16": (c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
     "icv_add_noise_f32": (c_int, [_P, _P, _P, _I, _F, c_int, _P]),
+    "icv_unpatchify_cfg_multistep": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, c_int, _F, _F, _F, _F, _F, _F, _F,
+                                             _I, _I, _I, _I, _I, _I, c_int, _P]),
 })
 
 class KVPiece(ctypes.Structure):

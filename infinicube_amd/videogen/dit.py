@@ -351,6 +351,7 @@ class WanDiT:
         self.t_mod = a((1, 6 * d), F32)
         self._t_cached = None
         self._tc_res = None                # TeaCache residuals, one f32 [n, d] per CFG branch (allocated on first use)
+        self._solver_state = None          # multistep sampler: x_hat + three x0-predictions, f32 latent-shaped (allocated on first use)
         # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
         # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
         self._lat_tok0, self._win_engines, self._win_next = None, {}, None
@@ -1022,6 +1023,7 @@ class WanDiT:
         t = copy.copy(self)
         t._pair, t._twin, t._native, t._graphs, t._graphs_on = None, None, None, {}, False
         t._lat_tok0, t._win_engines, t._win_next = None, {}, None
+        t._solver_state = None
         return t
 
     def _pair_engine(self):
@@ -1081,6 +1083,12 @@ class WanDiT:
             self._tc_res = (self.ops.alloc((n, d), F32), self.ops.alloc((n, d), F32))
         return self._tc_res
 
+    def _solver_buffers(self, latent: torch.Tensor):
+        """(x_hat, [three x0-prediction slots]) of the multistep sampler: f32, the latent's shape, once per prepared grid."""
+        if self._solver_state is None or self._solver_state[0].shape != latent.shape:
+            self._solver_state = (self.ops.alloc(tuple(latent.shape), F32), [self.ops.alloc(tuple(latent.shape), F32) for _ in range(3)])
+        return self._solver_state
+
     def _tc_store(self, patches: torch.Tensor, x: torch.Tensor, r: torch.Tensor):
         """r = x - (patches @ patch_w.T + patch_b): the residual of a computed forward whose stream ended in ``x``."""
         self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
@@ -1120,7 +1128,7 @@ class WanDiT:
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
-                branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None) -> torch.Tensor:
+                branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1131,8 +1139,18 @@ class WanDiT:
         residual the last computed step stored (one [n, d] f32 buffer per CFG branch).  None: every step is computed.
         ``sliding_window`` (sliding_window.WindowPlan over the T frames of ``latent``): with more than one window, every step runs
         the forwards on each temporal window and blends their updates (_denoise_windows); this engine must be prepared for a
-        window's grid, ``buf_tokens`` are the whole clip's (embed_buffers(whole_clip=True)).  None or ONE window: this loop."""
+        window's grid, ``buf_tokens`` are the whole clip's (embed_buffers(whole_clip=True)).  None or ONE window: this loop.
+        ``solver`` (solver.MultistepPlan over the scheduler's sigmas): the step's last launch is icv_unpatchify_cfg_multistep with the
+        plan's coefficients instead of the Euler update; its state (x_hat and three x0-predictions, latent-shaped) lives for this
+        call, and the first step the call executes is the solver's first step.  None: the Euler update."""
         ops, plan = self.ops, self.plan
+        if solver is not None:
+            for on, what in ((sliding_window is not None and len(sliding_window.windows) > 1, "more than one sliding temporal window"),
+                             (self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)")):
+                if on:
+                    raise ValueError(f"sample_solver={solver.name!r} cannot be combined with {what} yet")
+            if len(solver.sigmas) != len(scheduler.sigmas) or any(a != b for a, b in zip(solver.sigmas, scheduler.sigmas)):
+                raise ValueError("denoise: the solver plan was not built on this scheduler's sigmas")
         if sliding_window is not None and len(sliding_window.windows) > 1 and self._framewin() is not None:
             raise ValueError("attention_window_frames cannot be combined with sliding_window_size in the same call yet")
         if sliding_window is not None and len(sliding_window.windows) > 1:
@@ -1152,6 +1170,7 @@ class WanDiT:
         else:
             use_cfg = ctx_uncond is not None and cfg_scale != 1.0
             ctxs, outs = [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], [self.head_out[0], self.head_out[1]]
+        run = solver.begin() if solver is not None else None
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
             ts = scheduler.timesteps[i]
             if res is not None and tea_cache.skip(i):
@@ -1164,8 +1183,14 @@ class WanDiT:
                         self._tc_store(patches, x, res[b])
             if branch_exchange is not None:
                 branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
-            ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1] if use_cfg else None,
-                                     cfg_scale, scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
+            if run is not None:
+                st, (x_hat, ring), k = run.step(i), self._solver_buffers(latent), len(run.done) - 1
+                ops.unpatchify_cfg_multistep(latent, x_hat, ring[k % 3], ring[(k - 1) % 3], ring[(k - 2) % 3], self.head_out[0],
+                                             self.head_out[1] if use_cfg else None, cfg_scale, st.sigma, st.a, st.c,
+                                             plan.tok0, plan.n_tok, round_bf16=round_bf16)
+            else:
+                ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1] if use_cfg else None,
+                                         cfg_scale, scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
             if self.sp_on:
                 self._check_transport()
             if on_step is not None:

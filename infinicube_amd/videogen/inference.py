@@ -156,6 +156,9 @@ class WanVideoGenerator:
             if getattr(self.pipe, "attention_window_frames", None) is not None or getattr(self.pipe, "attention_sink_frames", None) is not None:
                 raise ValueError("attention_window_frames / attention_sink_frames (ICV_ATTN_WINDOW_FRAMES / ICV_ATTN_SINK_FRAMES) cannot be "
                                  "combined with ICV_WORLD > 1 (the frame-windowed launch is single-rank) yet")
+            if getattr(self.pipe, "sample_solver", None) not in (None, "euler"):
+                raise ValueError("sample_solver (ICV_SAMPLE_SOLVER) cannot be combined with ICV_WORLD > 1 (the multistep update is "
+                                 "single-rank) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

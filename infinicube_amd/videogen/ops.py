@@ -385,6 +385,28 @@ class HipOps:
             latent.data_ptr(), native.ptr(vel_out), hc.data_ptr(), native.ptr(hu), hc.stride(0),
             cfg_scale, dsigma, C, T, H8, W8, tok0, n_tok, int(bool(round_bf16)), self._stream()), "icv_unpatchify_cfg_euler")
 
+    def unpatchify_cfg_multistep(self, latent, x_hat, m_new, m_prev, m_prev2, hc, hu, cfg_scale, sigma, a, c, tok0, n_tok, round_bf16=False):
+        """Multistep samplers (solver.py): for the local tokens, m_new = latent - sigma * CFG(hc, hu); x_hat <- x_c = a . (x_hat, m_prev,
+        m_prev2, m_new) (``a`` None: x_c = latent); latent <- c . (x_c, m_new, m_prev).  Five different f32 latent-shaped buffers;
+        m_prev / m_prev2 may be None where their coefficients are 0."""
+        bufs = dict(latent=latent, x_hat=x_hat, m_new=m_new, m_prev=m_prev, m_prev2=m_prev2)
+        for name, t in bufs.items():
+            if t is None and name in ("m_prev", "m_prev2"):
+                continue
+            _chk(t, F32, f"multistep.{name}")
+            if not t.is_contiguous() or tuple(t.shape) != tuple(latent.shape):
+                raise ValueError(f"unpatchify_cfg_multistep: {name} must be a contiguous tensor of the latent's shape {tuple(latent.shape)}")
+        _chk(hc, F32, "multistep.hc")
+        if hc.shape[0] < n_tok or (hu is not None and (hu.shape[0] < n_tok or hu.stride(0) != hc.stride(0))):
+            raise ValueError("unpatchify_cfg_multistep: head outputs have fewer rows than n_tok (or differ in row stride)")
+        C, T, H8, W8 = latent.shape
+        a4 = (0.0, 0.0, 0.0, 0.0) if a is None else tuple(float(x) for x in a)
+        c3 = tuple(float(x) for x in c)
+        native.check(self.lib.icv_unpatchify_cfg_multistep(
+            latent.data_ptr(), x_hat.data_ptr(), m_new.data_ptr(), native.ptr(m_prev), native.ptr(m_prev2), hc.data_ptr(), native.ptr(hu),
+            hc.stride(0), cfg_scale, float(sigma), int(a is not None), *a4, *c3, C, T, H8, W8, tok0, n_tok, int(bool(round_bf16)),
+            self._stream()), "icv_unpatchify_cfg_multistep")
+
     def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
         """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
         window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""

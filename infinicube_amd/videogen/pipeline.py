@@ -305,6 +305,18 @@ class WanVideoPipeline:
         self.attention_window_frames: Optional[int] = _aw.env_int(_aw.ENV_WINDOW, os.environ.get(_aw.ENV_WINDOW))
         self.attention_sink_frames: Optional[int] = _aw.env_int(_aw.ENV_SINK, os.environ.get(_aw.ENV_SINK))
         self.attention_window_record: Optional[dict] = None
+        # Multistep sampler (solver.py; Wan2.1's keyword of the same name): "unipc" replaces the Euler update that ends
+        # a step, same two forwards per step.  None / "euler" = today's path.  The caller of the unchanged WanVideoGenerator opts in
+        # with ICV_SAMPLE_SOLVER, and sets the step count of ANY solver with ICV_SAMPLE_STEPS (an integer >= 1; unset = 50).
+        # pipe.solver_record: {"name", "steps", "orders"} of the last call (None when it ran Euler steps).
+        from . import solver as _solver
+        self.sample_solver: Optional[str] = os.environ.get(_solver.ENV_SOLVER) or None
+        _solver.validate(self.sample_solver)
+        env_steps = _solver.env_steps(os.environ.get(_solver.ENV_STEPS))
+        if env_steps is not None:
+            self.num_inference_steps = env_steps
+            self.scheduler = FlowMatchScheduler(self.num_inference_steps, self.sigma_shift, self.reference_rounding)
+        self.solver_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -516,7 +528,7 @@ class WanVideoPipeline:
                  tea_cache_model_id: str = "", sliding_window_size: Optional[int] = None,
                  sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
-                 **unused):
+                 sample_solver: Optional[str] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
@@ -540,6 +552,12 @@ class WanVideoPipeline:
             raise ValueError("attention_window_frames / attention_sink_frames cannot be combined with the e4m3 self-attention mode "
                              "(torch_dtype=float8_e4m3fn) yet")
         self.attention_window_record = None
+        # multistep sampler: the name is validated here, its scope below, both before any GPU work
+        from . import solver as _solver
+        solver_name = _solver.validate(self.sample_solver if sample_solver is None else sample_solver)
+        self.solver_record = None
+        if solver_name is not None and sw_plan is not None:
+            raise ValueError(f"sample_solver={solver_name!r} cannot be combined with sliding_window_size (more than one window) in the same call yet")
         # video-to-video: the clip is read (a path) and both settings are checked here, before any GPU work
         from . import v2v
         v2v_frames, strength = v2v.validate(self.input_video if input_video is None else input_video,
@@ -563,6 +581,8 @@ class WanVideoPipeline:
                     raise ValueError(f"sliding_window_size / sliding_window_stride cannot be combined with {what} yet")
         if aw is not None and world > 1:
             raise ValueError(f"attention_window_frames / attention_sink_frames cannot be combined with a process group of {world} ranks yet")
+        if solver_name is not None and world > 1:
+            raise ValueError(f"sample_solver={solver_name!r} cannot be combined with a process group of {world} ranks yet")
         if v2v_frames is not None and world > 1:
             raise ValueError(f"input_video / denoising_strength cannot be combined with a process group of {world} ranks yet")
         engine = self._get_engine()
@@ -683,13 +703,18 @@ class WanVideoPipeline:
                 dist.broadcast_object_list(box, src=0)
                 tc_plan = box[0]
         self.tea_cache_record = tc_plan.record() if tc_plan is not None else None
+        solver_plan = None
+        if solver_name is not None:
+            solver_plan = _solver.MultistepPlan(solver_name, self.scheduler.sigmas)
+            self.solver_record = solver_plan.record(range(num_inference_steps))
         # the hot loop (HIP)
         it = range(num_inference_steps)
         if progress_bar_cmd is not None:
             it = progress_bar_cmd(it)
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
-                       round_bf16=self.reference_rounding, tea_cache=tc_plan, **(dict(sliding_window=sw_plan) if sw_plan is not None else {}))
+                       round_bf16=self.reference_rounding, tea_cache=tc_plan, **(dict(sliding_window=sw_plan) if sw_plan is not None else {}),
+                       **(dict(solver=solver_plan) if solver_plan is not None else {}))
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
         # The DECODE is sharded (a collective of every rank: vae.TileShard broadcasts the tiles) only where every rank is known to
         # take part: behind a multigpu.WorkerPool (its workers pass join_decode=True) or when the caller says so
