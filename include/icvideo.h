@@ -38,7 +38,8 @@ extern "C" {
  *    signature changed.  Later additions under 5 (additive exports only): icv_sub_rows_f32 and icv_rel_l1_steps_f32 (TeaCache step skipping);
  *    icv_unpatchify_cfg_euler_window (sliding temporal windows); icv_lora_merge_bf16 (LoRA merge in HBM); icv_add_noise_f32
  *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch);
- *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms). */
+ *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms);
+ *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -293,6 +294,23 @@ int icv_unpatchify_cfg_multistep(float* latent, float* x_hat, float* m_new, cons
                                  const float* hc, const float* hu, int64_t ldh, float cfg_scale, float sigma, int corrector,
                                  float a0, float a1, float a2, float a3, float c0, float c1, float c2, int64_t C, int64_t T,
                                  int64_t H8, int64_t W8, int64_t tok0, int64_t n_tok, int round_bf16, void* stream);
+
+/* ---- CFG-Zero* guidance: the optimised scale, reduced and applied on the device ----
+ * hc, hu: f32 [rows, cols] with row stride ldh >= cols (elements); hc is read only.  With the sums taken over all rows * cols
+ * elements in fp64 (a product of two f32 values is exact there):
+ *     s  = (float)( sum hc * hu / (sum hu * hu + 1e-8) )        -> scale_out[0]   (sum hu * hu == 0 gives s = 0, not NaN)
+ *     hu <- s * hu                                              in place, one f32 rounding per element
+ * Columns >= cols of a row and rows >= rows are not touched.  Two launches on ``stream``: the first leaves one pair of partial
+ * sums per block in ``workspace`` (ICV_CFG_ZERO_WORKSPACE_DOUBLES doubles, 8-byte aligned, device memory), the second adds them
+ * in one fixed order in every block.  No atomics and no host read; the grid and the assignment of elements to threads depend on
+ * (rows, cols) only, so the same inputs give the same bits, whatever the pointers' alignment (16-byte loads are used where hc, hu
+ * and ldh allow them; any 4-byte-aligned pointers and any ldh work).
+ * round_bf16 != 0 ("reference rounding"): the sums are taken on the bf16-rounded hc and hu, s is rounded to bf16 and
+ * hu <- bf16(s * bf16(hu)); values stay in f32 storage, sums in fp64.
+ * Every argument check runs on the host before the first launch. */
+#define ICV_CFG_ZERO_WORKSPACE_DOUBLES 512
+int icv_cfg_zero_scale_f32(const float* hc, float* hu, int64_t ldh, int64_t rows, int64_t cols, double* workspace,
+                           float* scale_out, int round_bf16, void* stream);
 
 /* ---- coordinate guidance buffer (producer of the hot path's input) ---------------
  * Replaces `generate_coordinate_buffer_from_memory_global_norm` [R infinicube/utils/buffer_utils.py:180-265]

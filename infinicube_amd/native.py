@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ICV_LIB_PATH") or os.path.join(_HERE, "csrc", "libicvideo.so")
 
 EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, EPI_F32 = 0, 1, 2, 3
+CFG_ZERO_WORKSPACE_DOUBLES = 512      # ICV_CFG_ZERO_WORKSPACE_DOUBLES (icv_cfg_zero_scale_f32's partial sums)
 ACT_NONE, ACT_SILU = 0, 1
 
 # name -> (restype, argtypes); must list EVERY symbol include/icvideo.h declares
@@ -114,6 +115,7 @@ SIGNATURES.update({
     "icv_add_noise_f32": (c_int, [_P, _P, _P, _I, _F, c_int, _P]),
     "icv_unpatchify_cfg_multistep": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, c_int, _F, _F, _F, _F, _F, _F, _F,
                                              _I, _I, _I, _I, _I, _I, c_int, _P]),
+    "icv_cfg_zero_scale_f32": (c_int, [_P, _P, _I, _I, _I, _P, _P, c_int, _P]),
 })
 
 class KVPiece(ctypes.Structure):

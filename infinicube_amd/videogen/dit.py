@@ -41,6 +41,7 @@ from typing import Dict, Optional
 
 import torch
 
+from ..native import CFG_ZERO_WORKSPACE_DOUBLES
 from .config import TokenGrid, WanDiTConfig
 from .ops import BF16, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32, F32, FP8, RopeTable
 from .scheduler import FlowMatchScheduler
@@ -352,6 +353,9 @@ class WanDiT:
         self._t_cached = None
         self._tc_res = None                # TeaCache residuals, one f32 [n, d] per CFG branch (allocated on first use)
         self._solver_state = None          # multistep sampler: x_hat + three x0-predictions, f32 latent-shaped (allocated on first use)
+        # CFG-Zero* (guidance.py): (fp64 partial-sum workspace, f32 [N] scales of a call's steps), allocated on first use;
+        # guidance_scales: the last guided call's scale per step (None for a step that computed none), None without guidance
+        self._guidance_state, self.guidance_scales = None, None
         # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
         # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
         self._lat_tok0, self._win_engines, self._win_next = None, {}, None
@@ -1024,6 +1028,7 @@ class WanDiT:
         t._pair, t._twin, t._native, t._graphs, t._graphs_on = None, None, None, {}, False
         t._lat_tok0, t._win_engines, t._win_next = None, {}, None
         t._solver_state = None
+        t._guidance_state, t.guidance_scales = None, None
         return t
 
     def _pair_engine(self):
@@ -1089,6 +1094,13 @@ class WanDiT:
             self._solver_state = (self.ops.alloc(tuple(latent.shape), F32), [self.ops.alloc(tuple(latent.shape), F32) for _ in range(3)])
         return self._solver_state
 
+    def _guidance_buffers(self, n_steps: int):
+        """(workspace f64 [ICV_CFG_ZERO_WORKSPACE_DOUBLES], scales f32 [>= n_steps]) of the CFG-Zero* scale: once per engine, again
+        only when a call has more steps than the array holds."""
+        if self._guidance_state is None or self._guidance_state[1].numel() < n_steps:
+            self._guidance_state = (self.ops.alloc((CFG_ZERO_WORKSPACE_DOUBLES,), torch.float64), self.ops.alloc((n_steps,), F32))
+        return self._guidance_state
+
     def _tc_store(self, patches: torch.Tensor, x: torch.Tensor, r: torch.Tensor):
         """r = x - (patches @ patch_w.T + patch_b): the residual of a computed forward whose stream ended in ``x``."""
         self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
@@ -1128,7 +1140,8 @@ class WanDiT:
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
-                branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None) -> torch.Tensor:
+                branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None,
+                guidance=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1142,8 +1155,23 @@ class WanDiT:
         window's grid, ``buf_tokens`` are the whole clip's (embed_buffers(whole_clip=True)).  None or ONE window: this loop.
         ``solver`` (solver.MultistepPlan over the scheduler's sigmas): the step's last launch is icv_unpatchify_cfg_multistep with the
         plan's coefficients instead of the Euler update; its state (x_hat and three x0-predictions, latent-shaped) lives for this
-        call, and the first step the call executes is the solver's first step.  None: the Euler update."""
+        call, and the first step the call executes is the solver's first step.  None: the Euler update.
+        ``guidance`` (guidance.GuidancePlan, CFG-Zero*): the steps ``i < zero_init_steps`` run no forward and no update (the latent's
+        bits stay; ``on_step`` still sees them), so the first executed step is the first step of the solver and of a TeaCache plan
+        (build both over the executed range).  With ``optimized_scale`` every executed step runs icv_cfg_zero_scale_f32 on the two
+        head outputs right in front of its update launch, on that launch's stream: s = <c, u> / (|u|^2 + 1e-8) into slot i of a
+        device array and ``head_out[1] <- s * head_out[1]`` IN PLACE (nothing reads the unconditional head output after the update).
+        The scales are read back once, after the loop, into ``self.guidance_scales``.  None: today's launches, allocations and bits."""
         ops, plan = self.ops, self.plan
+        self.guidance_scales = None
+        if guidance is not None:
+            for on, what in ((sliding_window is not None and len(sliding_window.windows) > 1, "more than one sliding temporal window"),
+                             (self.sp_on or plan.world > 1 or branch_exchange is not None,
+                              "sequence / CFG-branch parallelism (world > 1): the moments would need an all-reduce")):
+                if on:
+                    raise ValueError(f"cfg_zero_star / cfg_zero_init_steps cannot be combined with {what} yet")
+            if guidance.optimized_scale and not (ctx_uncond is not None and cfg_scale != 1.0):
+                raise ValueError("cfg_zero_star needs classifier-free guidance (an unconditional context and cfg_scale != 1)")
         if solver is not None:
             for on, what in ((sliding_window is not None and len(sliding_window.windows) > 1, "more than one sliding temporal window"),
                              (self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)")):
@@ -1171,7 +1199,17 @@ class WanDiT:
             use_cfg = ctx_uncond is not None and cfg_scale != 1.0
             ctxs, outs = [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], [self.head_out[0], self.head_out[1]]
         run = solver.begin() if solver is not None else None
+        gd_scale = guidance is not None and guidance.optimized_scale
+        gd_steps = []                                                  # the steps of this call, and whether each one computed a scale
+        gd_work = gd_out = None                                        # allocated at the first scaled step, after everything else
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
+            if guidance is not None:
+                if guidance.skips(i):                                  # zero-init: the velocity is zero, so nothing runs
+                    gd_steps.append((i, False))
+                    if on_step is not None:
+                        on_step(i, latent)
+                    continue
+                gd_steps.append((i, gd_scale))
             ts = scheduler.timesteps[i]
             if res is not None and tea_cache.skip(i):
                 # TeaCache: no blocks, so no K|V exchange either (every rank skips the same steps); both branches on this stream
@@ -1183,6 +1221,10 @@ class WanDiT:
                         self._tc_store(patches, x, res[b])
             if branch_exchange is not None:
                 branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
+            if gd_scale:
+                if gd_out is None:
+                    gd_work, gd_out = self._guidance_buffers(len(scheduler.sigmas))
+                ops.cfg_zero_scale(self.head_out[0], self.head_out[1], plan.n_tok, gd_work, gd_out[i: i + 1], round_bf16=round_bf16)
             if run is not None:
                 st, (x_hat, ring), k = run.step(i), self._solver_buffers(latent), len(run.done) - 1
                 ops.unpatchify_cfg_multistep(latent, x_hat, ring[k % 3], ring[(k - 1) % 3], ring[(k - 2) % 3], self.head_out[0],
@@ -1197,6 +1239,9 @@ class WanDiT:
                 on_step(i, latent)
         if self.sp_on:
             self.check_exchange()
+        if guidance is not None:
+            got = gd_out.cpu().tolist() if gd_out is not None else None      # the one read-back of the call
+            self.guidance_scales = [float(got[i]) if on else None for i, on in gd_steps]
         return latent
 
     # ------------------------------------------------------------------------------------

@@ -159,6 +159,9 @@ class WanVideoGenerator:
             if getattr(self.pipe, "sample_solver", None) not in (None, "euler"):
                 raise ValueError("sample_solver (ICV_SAMPLE_SOLVER) cannot be combined with ICV_WORLD > 1 (the multistep update is "
                                  "single-rank) yet")
+            if getattr(self.pipe, "cfg_zero_star", None) or getattr(self.pipe, "cfg_zero_init_steps", None):
+                raise ValueError("cfg_zero_star / cfg_zero_init_steps (ICV_CFG_ZERO_STAR / ICV_CFG_ZERO_INIT_STEPS) cannot be combined with "
+                                 "ICV_WORLD > 1 (the scale's moments are single-rank) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -407,6 +407,19 @@ class HipOps:
             hc.stride(0), cfg_scale, float(sigma), int(a is not None), *a4, *c3, C, T, H8, W8, tok0, n_tok, int(bool(round_bf16)),
             self._stream()), "icv_unpatchify_cfg_multistep")
 
+    def cfg_zero_scale(self, hc, hu, n_tok, workspace, scale_out, round_bf16=False):
+        """CFG-Zero* optimised scale (guidance.py): over the first n_tok rows of the head outputs hc, hu (f32 [>= n_tok, 4*C], equal
+        row strides), scale_out[0] = s = <hc, hu> / (|hu|^2 + 1e-8) and hu <- s * hu IN PLACE (icv_cfg_zero_scale_f32: fp64 sums, two
+        launches, no host read).  workspace: f64 [ICV_CFG_ZERO_WORKSPACE_DOUBLES]; scale_out: f32, one element."""
+        _chk(hc, F32, "cfg_zero_scale.hc"); _chk(hu, F32, "cfg_zero_scale.hu"); _chk(scale_out, F32, "cfg_zero_scale.scale_out")
+        _chk(workspace, torch.float64, "cfg_zero_scale.workspace")
+        if hc.dim() != 2 or hu.dim() != 2 or hc.shape[1] != hu.shape[1] or hc.shape[0] < n_tok or hu.shape[0] < n_tok or hu.stride(0) != hc.stride(0):
+            raise ValueError("cfg_zero_scale: head outputs have fewer rows than n_tok (or differ in width or row stride)")
+        if workspace.numel() < native.CFG_ZERO_WORKSPACE_DOUBLES or not workspace.is_contiguous() or scale_out.numel() != 1:
+            raise ValueError(f"cfg_zero_scale: workspace must hold {native.CFG_ZERO_WORKSPACE_DOUBLES} contiguous doubles and scale_out one float")
+        native.check(self.lib.icv_cfg_zero_scale_f32(hc.data_ptr(), hu.data_ptr(), hc.stride(0), n_tok, hc.shape[1], workspace.data_ptr(),
+                                                     scale_out.data_ptr(), int(bool(round_bf16)), self._stream()), "icv_cfg_zero_scale_f32")
+
     def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
         """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
         window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""

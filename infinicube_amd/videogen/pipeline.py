@@ -317,6 +317,15 @@ class WanVideoPipeline:
             self.num_inference_steps = env_steps
             self.scheduler = FlowMatchScheduler(self.num_inference_steps, self.sigma_shift, self.reference_rounding)
         self.solver_record: Optional[dict] = None
+        # CFG-Zero* guidance (guidance.py): cfg_zero_star scales the unconditional velocity of every step by its
+        # projection coefficient onto the conditional one before the CFG combine; cfg_zero_init_steps = K runs nothing in the first K
+        # steps.  Off by default; the caller of the unchanged WanVideoGenerator opts in with ICV_CFG_ZERO_STAR (0 / 1) and
+        # ICV_CFG_ZERO_INIT_STEPS (an integer >= 0).  pipe.guidance_record: {"optimized_scale", "zero_init_steps", "scales"} of the
+        # last call (None when both were off).
+        from . import guidance as _guidance
+        self.cfg_zero_star: Optional[bool] = _guidance.env_star(os.environ.get(_guidance.ENV_STAR))
+        self.cfg_zero_init_steps: Optional[int] = _guidance.env_init_steps(os.environ.get(_guidance.ENV_INIT_STEPS))
+        self.guidance_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -528,7 +537,8 @@ class WanVideoPipeline:
                  tea_cache_model_id: str = "", sliding_window_size: Optional[int] = None,
                  sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
-                 sample_solver: Optional[str] = None, **unused):
+                 sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
+                 cfg_zero_init_steps: Optional[int] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
@@ -558,6 +568,15 @@ class WanVideoPipeline:
         self.solver_record = None
         if solver_name is not None and sw_plan is not None:
             raise ValueError(f"sample_solver={solver_name!r} cannot be combined with sliding_window_size (more than one window) in the same call yet")
+        # CFG-Zero* guidance: values here, scope below, both before any GPU work
+        from . import guidance as _guidance
+        gd_plan = _guidance.validate(self.cfg_zero_star if cfg_zero_star is None else cfg_zero_star,
+                                     self.cfg_zero_init_steps if cfg_zero_init_steps is None else cfg_zero_init_steps,
+                                     num_inference_steps, cfg_scale)
+        self.guidance_record = None
+        if gd_plan is not None and sw_plan is not None:
+            raise ValueError("cfg_zero_star / cfg_zero_init_steps cannot be combined with sliding_window_size (more than one window) in the same call yet")
+        first_step = gd_plan.zero_init_steps if gd_plan is not None else 0        # the first step that runs: where solver and TeaCache begin
         # video-to-video: the clip is read (a path) and both settings are checked here, before any GPU work
         from . import v2v
         v2v_frames, strength = v2v.validate(self.input_video if input_video is None else input_video,
@@ -583,6 +602,8 @@ class WanVideoPipeline:
             raise ValueError(f"attention_window_frames / attention_sink_frames cannot be combined with a process group of {world} ranks yet")
         if solver_name is not None and world > 1:
             raise ValueError(f"sample_solver={solver_name!r} cannot be combined with a process group of {world} ranks yet")
+        if gd_plan is not None and world > 1:
+            raise ValueError(f"cfg_zero_star / cfg_zero_init_steps cannot be combined with a process group of {world} ranks yet")
         if v2v_frames is not None and world > 1:
             raise ValueError(f"input_video / denoising_strength cannot be combined with a process group of {world} ranks yet")
         engine = self._get_engine()
@@ -697,7 +718,7 @@ class WanVideoPipeline:
         if tc_thresh is not None:
             from . import teacache
             if rank == 0:
-                tc_plan = teacache.plan(engine, self.scheduler, tc_thresh, tc_id, range(num_inference_steps))
+                tc_plan = teacache.plan(engine, self.scheduler, tc_thresh, tc_id, range(first_step, num_inference_steps))
             if world > 1:
                 box = [tc_plan]
                 dist.broadcast_object_list(box, src=0)
@@ -706,7 +727,7 @@ class WanVideoPipeline:
         solver_plan = None
         if solver_name is not None:
             solver_plan = _solver.MultistepPlan(solver_name, self.scheduler.sigmas)
-            self.solver_record = solver_plan.record(range(num_inference_steps))
+            self.solver_record = solver_plan.record(range(first_step, num_inference_steps))
         # the hot loop (HIP)
         it = range(num_inference_steps)
         if progress_bar_cmd is not None:
@@ -714,7 +735,10 @@ class WanVideoPipeline:
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
                        round_bf16=self.reference_rounding, tea_cache=tc_plan, **(dict(sliding_window=sw_plan) if sw_plan is not None else {}),
-                       **(dict(solver=solver_plan) if solver_plan is not None else {}))
+                       **(dict(solver=solver_plan) if solver_plan is not None else {}),
+                       **(dict(guidance=gd_plan) if gd_plan is not None else {}))
+        if gd_plan is not None:
+            self.guidance_record = gd_plan.record(engine.guidance_scales)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
         # The DECODE is sharded (a collective of every rank: vae.TileShard broadcasts the tiles) only where every rank is known to
         # take part: behind a multigpu.WorkerPool (its workers pass join_decode=True) or when the caller says so
