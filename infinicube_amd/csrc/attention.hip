@@ -131,6 +131,22 @@ extern "C" int icv_attention_fwd_add(const void* q, int64_t ldq, const void* k, 
   return attn_route(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, nullptr, 0, 2, Sq, Skv, heads, scale, (hipStream_t)stream);
 }
 
+// MFMA shape of the bf16 kernels attn7.hip and attn7p.hip (icv_set_option("attn_mfma", n)): 32 = v_mfma_f32_32x32x16_bf16, 16 =
+// v_mfma_f32_16x16x32_bf16 at the same wave tile; a negative value = the default.  The two kernels read it HERE, so the long-key
+// launches (attn7p and attn7's 8-wave kernel, pinned to each other bit for bit by tests/test_attn_pieces_gpu.py) always agree.  The
+// short-key shape of attn7.hip (cross-attention) has a default of its own; an explicit value applies to it as well.
+// Defaults: 16 for both - every round of the 16 arm beat every round of the 32 arm at the 14B self-attention (22.60 vs 23.17 ms), its two
+// shard shapes and the 512-key cross-attention (interleaved in one process, tools/attn_mfma_ab.py; profiles/attn_mfma16/README.md).
+constexpr int ATTN_MFMA_DEFAULT = 16;
+constexpr int ATTN_MFMA_SHORT_DEFAULT = 16;
+int icv_attn_mfma(bool short_kv) {
+  const int v = icv_get_option_int("attn_mfma", -1);
+  if (v < 0) return short_kv ? ATTN_MFMA_SHORT_DEFAULT : ATTN_MFMA_DEFAULT;
+  if (v == 16 || v == 32) return v;
+  icv_set_error("attn_mfma = %d: the MFMA shape is 16 (16x16x32) or 32 (32x32x16); negative = the default", v);
+  return -1;
+}
+
 // ---- diagnostics: where and when every work-group of the NEXT attn7 launches runs -----------------------------------------
 // icv_attention_trace(buf, capacity): buf = device u64 [capacity][4] (NULL switches tracing off).  While set, every attn7
 // work-group b < capacity writes buf[b] = {start, end (s_memrealtime ticks, 100 MHz), HW_ID, XCC_ID} - the round structure and

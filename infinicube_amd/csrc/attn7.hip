@@ -8,6 +8,11 @@
 //   * DMA addresses: tile base in an SGPR pair + four fixed 32-bit per-lane byte offsets (saddr form of
 //     global_load_lds_dwordx4); only a partial last tile takes the clamped 64-bit path.
 // Everything else (fragments, swizzled LDS images, ring invariants, stagger option) is experiments/attn4.hip's: see there.
+// MFMA shape (template MF, option "attn_mfma", default 16): the body in this file is the 32x32x16 form (MF = 32).  MF = 16 runs the same
+// wave tile (32 query rows x 64 keys), ring, DMA and softmax on v_mfma_f32_16x16x32_bf16 - 32 + 32 MFMAs per key tile instead of 16 + 16,
+// the same 16 ds_read_b128 and 32 ds_read_b64_tr_b16, a V image swizzled by (key & 7) - through attc::tile16 (attn_common.h: lane maps,
+// fragment prefetch), which attn7p.hip runs too.  Under the power limit the shape costs less energy per FLOP: 2.5 % of the 14B
+// self-attention launch, 5 % of the 512-key cross-attention (profiles/attn_mfma16/README.md).
 #include "attn_common.h"
 
 namespace att7 {
@@ -65,8 +70,12 @@ __device__ __forceinline__ void dma16s(const void* base, unsigned off, unsigned 
 //   <4, 2> (short key sequences, i.e. the 512 / 257-key cross-attention, option "attn7_short"): 128 rows, 64 KiB, so TWO
 //          blocks share a CU and one block's prologue (Q load, ring fill) and epilogue (O store) - half of a launch that
 //          has only 8 key tiles per row - run under the other's MFMAs; DMA one interval ahead, vmcnt(0) + barrier per tile.
-template <int VAR, int NW, int NST>
+// MF (option "attn_mfma"): 32 = v_mfma_f32_32x32x16_bf16, the body below; 16 = v_mfma_f32_16x16x32_bf16 at the same wave tile, ring and
+// softmax: attc::tile16 and its lane maps in attn_common.h (a lane then carries TWO query rows, q and q + 16; the V image's swizzle
+// differs, see there), shared with attn7p.hip so that the two kernels stay bit-identical at either shape.
+template <int VAR, int NW, int NST, int MF>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7_kernel(Params p) {
+  static_assert(MF == 16 || MF == 32, "MF: 16 (16x16x32 MFMAs) or 32 (32x32x16)");
   constexpr bool STAGGER = VAR & 1, KPREFETCH = VAR & 2, SETPRIO = VAR & 4, DEEP = VAR & 8, UNIT = VAR & 16;
   // QK^T MFMA order: d-step major (consecutive MFMAs share the Q fragment: less operand toggling, +0.6...1.4 % under the power
   // cap, profiles/r02/attention_variants.md) unless bit 32 asks for round 1's key-block-major order
@@ -103,8 +112,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   // ---- softmax state ----
   f32x16 ot[4];
-  float m_run, l_run;
-  attc::load_state(p, qr_c, head, hi, ot, m_run, l_run);
+  float m_run = NEG_BIG, l_run = 0.f;
+  attc::Tile16 s16;                  // MF == 16: state, reference and Q fragments of the wave's two 16-row q-blocks
+  int64_t qr16[2] = {0, 0};
+  if constexpr (MF == 16) {
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      const int64_t r = q0 + qb * 16 + (lane & 15);
+      qr16[qb] = r < p.Sq ? r : p.Sq - 1;
+    }
+    attc::tile16_init<UNIT>(p, qr16, head, lane >> 4, s16);
+  } else {
+    attc::load_state(p, qr_c, head, hi, ot, m_run, l_run);
+  }
   float m_base = m_run < -1.0e29f ? 0.f : m_run;   // UNIT: the reference currently baked into cinit
   f32x16 cinit;
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -113,7 +133,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   bf16x8 qf[8];
 #define A7_LOAD_Q()                                                                                   \
-  {                                                                                                   \
+  if constexpr (MF == 16) attc::tile16_load_q(p, qr16, head, lane >> 4, s16);                          \
+  else {                                                                                              \
     const bf16_t* qp = qh + qr_c * p.ldq + hi * 8;                                                    \
     _Pragma("unroll") for (int ds = 0; ds < 8; ++ds) qf[ds] = *reinterpret_cast<const bf16x8*>(qp + ds * 16); \
   }
@@ -134,7 +155,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   for (int j = 0; j < NI; ++j) {
     dkey[j] = (wave * NI + j) * 4 + (lane >> 4);
     kcol[j] = (pc ^ (dkey[j] & 15)) * 8;
-    vcol[j] = (pc ^ ((dkey[j] & 3) << 2)) * 8;
+    vcol[j] = MF == 16 ? attc::tile16_vcol(pc, dkey[j]) : (pc ^ ((dkey[j] & 3) << 2)) * 8;
     ko[j] = (unsigned)(((int64_t)dkey[j] * p.ldk + kcol[j]) * 2);
     vo[j] = (unsigned)(((int64_t)dkey[j] * p.ldv + vcol[j]) * 2);
   }
@@ -206,6 +227,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     const char* ks = smem + (t & (NST - 1)) * STAGE_BYTES;
     const char* vs = ks + TILE_BYTES;
     const int64_t key0 = (int64_t)t * KVB;
+    if constexpr (MF == 16) {
+      attc::tile16<UNIT, KPREFETCH, DSMAJOR, SETPRIO>(p, p_lim, ks, vs, key0, p.Skv, lane, s16);
+      return;
+    }
 
     f32x16 st[2];
     const bool no_ref = UNIT && m_run < -1.0e29f;
@@ -361,7 +386,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the tail DMAs before the LDS is released
   if (grp == 0 && STAGGER) A7_BARRIER();             // re-balance the stagger
 
-  attc::store_result(p, q0 + l31, head, hi, ot, m_run, l_run);
+  if constexpr (MF == 16) {
+    int t16 = lane & 15;
+    asm volatile("" : "+v"(t16));      // recompute the rows here: carried from the prologue they cost four VGPRs through the whole loop
+    const int64_t qr[2] = {q0 + t16, q0 + 16 + t16};
+    attc::store_result(p, qr, head, lane >> 4, s16.ot, s16.m_run, s16.l_run);
+  } else {
+    attc::store_result(p, q0 + l31, head, hi, ot, m_run, l_run);
+  }
   if (p.trace && tid == 0 && (int)blockIdx.x < p.trace_cap) {      // diagnostics: where and when did this work-group run
     unsigned hwid, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -371,14 +403,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   }
 }
 
-template <int VAR, int NW = 8, int NST = 4>
-int launch(const Params& p, hipStream_t st) {
+template <int VAR, int NW, int NST, int MF>
+int launch_mf(const Params& p, hipStream_t st) {
   constexpr int LDS_BYTES = NST * STAGE_BYTES;   // 128 KiB (one block per CU) or 64 KiB (two)
   static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7_kernel<VAR, NW, NST>, LDS_BYTES, &attr_set, "attn7")) return rc;
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7_kernel<VAR, NW, NST, MF>, LDS_BYTES, &attr_set, "attn7")) return rc;
   const int64_t nwg = (int64_t)p.heads * p.nqb;
-  hipLaunchKernelGGL((attn7_kernel<VAR, NW, NST>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, p);
+  hipLaunchKernelGGL((attn7_kernel<VAR, NW, NST, MF>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, p);
   return icv_check_launch("icv_attention(7)");
+}
+
+template <int VAR, int NW = 8, int NST = 4>
+int launch(const Params& p, hipStream_t st, int mf) {
+  return mf == 16 ? launch_mf<VAR, NW, NST, 16>(p, st) : launch_mf<VAR, NW, NST, 32>(p, st);
 }
 
 }  // namespace att7
@@ -397,28 +434,31 @@ int icv_attn7_dispatch(const void* q, int64_t ldq, const void* k, int64_t ldk, c
   if (p.sc == 1.0f && icv_get_option_int("attn_unit_scale", 1)) var |= 16;
   p.ablate = icv_get_option_int("attn7_ablate", 0);   // timing experiments only (tools/attn_bench.py)
   p.trace = icv_attention_trace_buffer(&p.trace_cap);
-  if (short_kv) return (var & 16) ? att7::launch<16, 4, 2>(p, st) : att7::launch<0, 4, 2>(p, st);
+  // MFMA shape (option "attn_mfma"): the long-key kernel always follows attn7p.hip; the short-key shape has its own default
+  const int mf = icv_attn_mfma(short_kv);
+  if (mf < 0) return 1;
+  if (short_kv) return (var & 16) ? att7::launch<16, 4, 2>(p, st, mf) : att7::launch<0, 4, 2>(p, st, mf);
   switch (var) {
-    case 0: return att7::launch<0>(p, st);
-    case 1: return att7::launch<1>(p, st);
-    case 4: return att7::launch<4>(p, st);
-    case 5: return att7::launch<5>(p, st);
-    case 6: return att7::launch<6>(p, st);
-    case 7: return att7::launch<7>(p, st);
-    case 8: return att7::launch<8>(p, st);
-    case 24: return att7::launch<24>(p, st);
-    case 32: return att7::launch<32>(p, st);
-    case 48: return att7::launch<48>(p, st);
-    case 128: return att7::launch<128>(p, st);
-    case 144: return att7::launch<144>(p, st);
-    case 132: return att7::launch<132>(p, st);
-    case 148: return att7::launch<148>(p, st);
-    case 16: return att7::launch<16>(p, st);
-    case 17: return att7::launch<17>(p, st);
-    case 20: return att7::launch<20>(p, st);
-    case 21: return att7::launch<21>(p, st);
-    case 22: return att7::launch<22>(p, st);
-    case 23: return att7::launch<23>(p, st);
+    case 0: return att7::launch<0>(p, st, mf);
+    case 1: return att7::launch<1>(p, st, mf);
+    case 4: return att7::launch<4>(p, st, mf);
+    case 5: return att7::launch<5>(p, st, mf);
+    case 6: return att7::launch<6>(p, st, mf);
+    case 7: return att7::launch<7>(p, st, mf);
+    case 8: return att7::launch<8>(p, st, mf);
+    case 24: return att7::launch<24>(p, st, mf);
+    case 32: return att7::launch<32>(p, st, mf);
+    case 48: return att7::launch<48>(p, st, mf);
+    case 128: return att7::launch<128>(p, st, mf);
+    case 144: return att7::launch<144>(p, st, mf);
+    case 132: return att7::launch<132>(p, st, mf);
+    case 148: return att7::launch<148>(p, st, mf);
+    case 16: return att7::launch<16>(p, st, mf);
+    case 17: return att7::launch<17>(p, st, mf);
+    case 20: return att7::launch<20>(p, st, mf);
+    case 21: return att7::launch<21>(p, st, mf);
+    case 22: return att7::launch<22>(p, st, mf);
+    case 23: return att7::launch<23>(p, st, mf);
   }
   icv_set_error("icv_attention_fwd: unknown attn7 variant %d", var);
   return 1;

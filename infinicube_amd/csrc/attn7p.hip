@@ -28,6 +28,9 @@
 // block of 256 rows of that frame): a block never straddles a frame, rows past the frame's end are clamped for reads and never stored
 // - what happens at Sq in the other instantiations.  Pieces are always there (no flags, no time-out, no error word): the ring runs
 // through the boundary between the two pieces as it does for a piece with flag < 0.
+// MFMA shape (template MF, option "attn_mfma", default 16): the tile in this file is the 32x32x16 form; MF = 16 runs attc::tile16
+// (attn_common.h) on v_mfma_f32_16x16x32_bf16 in every instantiation - same ring, pieces, flags and softmax; the carried state in memory
+// is one format for both.  22.60 vs 23.17 ms at the 14B self-attention (profiles/attn_mfma16/README.md).
 // Replaces: the chunked icv_attention_fwd_chunk sequence of the sequence-parallel self-attention (the fork's / xDiT-USP's gather-then-
 // flash_attention [EXT]); the reference itself has no such path (one GPU, [R infinicube/inference/guidance_buffer_generation.py:759-766]).
 #include "attn_common.h"
@@ -100,8 +103,11 @@ __device__ __forceinline__ unsigned load_flag_async(const unsigned* f) {
 }
 
 // FW: the frame-windowed instantiation (see the head of this file)
-template <bool UNIT, bool FW = false>
+// MF (option "attn_mfma"): 32 = v_mfma_f32_32x32x16_bf16, the tile below; 16 = v_mfma_f32_16x16x32_bf16 at the same wave tile, ring and
+// softmax: attc::tile16 (attn_common.h, lane maps there), the tile attn7.hip runs at MF = 16 - the two stay bit-identical at either shape
+template <bool UNIT, bool FW, int MF>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7p_kernel(Params pp) {
+  static_assert(MF == 16 || MF == 32, "MF: 16 (16x16x32 MFMAs) or 32 (32x32x16)");
   const attc::Params& p = pp.a;
   const float p_lim = __builtin_amdgcn_exp2f(p.thr);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -146,8 +152,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   // ---- softmax state (registers, across all pieces) ----
   f32x16 ot[4];
-  float m_run, l_run;
-  attc::load_state(p, qr_c, head, hi, ot, m_run, l_run);
+  float m_run = NEG_BIG, l_run = 0.f;
+  attc::Tile16 s16;                  // MF == 16: state, reference and Q fragments of the wave's two 16-row q-blocks
+  int64_t qr16[2] = {0, 0};
+  if constexpr (MF == 16) {
+    const int64_t q_lim = FW ? q_end : p.Sq;
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      const int64_t r = q0 + qb * 16 + (lane & 15);
+      qr16[qb] = r < q_lim ? r : q_lim - 1;
+    }
+    attc::tile16_init<UNIT>(p, qr16, head, lane >> 4, s16);
+  } else {
+    attc::load_state(p, qr_c, head, hi, ot, m_run, l_run);
+  }
   float m_base = m_run < -1.0e29f ? 0.f : m_run;
   f32x16 cinit;
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -155,7 +173,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   for (int r = 0; r < 16; ++r) cinit[r] = UNIT ? -m_base : 0.f;
 
   bf16x8 qf[8];
-  {
+  if constexpr (MF == 16) attc::tile16_load_q(p, qr16, head, lane >> 4, s16);
+  else {
     const bf16_t* qp = qh + qr_c * p.ldq + hi * 8;
 #pragma unroll
     for (int ds = 0; ds < 8; ++ds) qf[ds] = *reinterpret_cast<const bf16x8*>(qp + ds * 16);
@@ -171,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   for (int j = 0; j < NI; ++j) {
     dkey[j] = (wave * NI + j) * 4 + (lane >> 4);
     kcol[j] = (pc ^ (dkey[j] & 15)) * 8;
-    vcol[j] = (pc ^ ((dkey[j] & 3) << 2)) * 8;
+    vcol[j] = MF == 16 ? attc::tile16_vcol(pc, dkey[j]) : (pc ^ ((dkey[j] & 3) << 2)) * 8;
     ko[j] = (unsigned)(((int64_t)dkey[j] * p.ldk + kcol[j]) * 2);
     vo[j] = (unsigned)(((int64_t)dkey[j] * p.ldv + vcol[j]) * 2);
   }
@@ -255,6 +274,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   auto tile = [&](const int stg, const int key0, const int skv) __attribute__((always_inline)) {
     const char* ks = smem + (stg & (NST - 1)) * STAGE_BYTES;
     const char* vs = ks + TILE_BYTES;
+    if constexpr (MF == 16) {
+      attc::tile16<UNIT, false, true, true>(p, p_lim, ks, vs, key0, skv, lane, s16);
+      return;
+    }
     f32x16 st[2];
     const bool no_ref = UNIT && m_run < -1.0e29f;
 #pragma unroll
@@ -346,6 +369,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   // ---- walk the pieces ----
   const int np = FW ? fw_np : __builtin_amdgcn_readfirstlane(pp.n_pieces);
+  // the host passes no empty list and no empty piece: without the path that skips the loops the register allocator no longer parks
+  // accumulators in scratch between prologue and epilogue (MF = 16 only: the 32 form's instruction stream stays what it was)
+  if constexpr (MF == 16) __builtin_assume(np >= 1);
   unsigned gt = 0;                 // ring position of the current piece's tile 0 (always even)
   unsigned iv = 0;                 // interval counter (verdict word parity)
   P_WAIT_PIECE(0);
@@ -357,6 +383,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   for (int pj = 0; pj < np; ++pj) {
     const int skv = P_ROWS(pj);
     const int nt = (skv + KVB - 1) / KVB;
+    if constexpr (MF == 16) __builtin_assume(nt >= 1);
     const unsigned g_next = gt + (unsigned)((nt + 1) & ~1);
     const bool has_next = pj + 1 < np;
     const int nflag = has_next && !FW ? __builtin_amdgcn_readfirstlane(pp.piece[has_next ? pj + 1 : pj].flag) : -1;
@@ -400,7 +427,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   // FW: a row past the frame's end belongs to the next frame's work-group - hand store_result a row it does not store
-  attc::store_result(p, !FW || q0 + l31 < q_end ? q0 + l31 : p.Sq, head, hi, ot, m_run, l_run);
+  if constexpr (MF == 16) {
+    int64_t qr[2];
+    int t16 = lane & 15;
+    asm volatile("" : "+v"(t16));      // recompute the rows here: carried from the prologue they cost four VGPRs through the whole loop
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      const int64_t r = q0 + qb * 16 + t16;
+      qr[qb] = !FW || r < q_end ? r : p.Sq;
+    }
+    attc::store_result(p, qr, head, lane >> 4, s16.ot, s16.m_run, s16.l_run);
+  } else {
+    attc::store_result(p, !FW || q0 + l31 < q_end ? q0 + l31 : p.Sq, head, hi, ot, m_run, l_run);
+  }
   if (p.trace && tid == 0 && (int)blockIdx.x < p.trace_cap) {
     unsigned hwid, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -415,13 +454,21 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #undef P_WAIT_PIECE
 }
 
+template <bool UNIT, bool FW, int MF>
+int launch_mf(const Params& pp, hipStream_t st) {
+  static icv_dev_flags attr_set = {};
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW, MF>, LDS_BYTES, &attr_set, "attn7p")) return rc;
+  const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
+  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW, MF>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
+  return icv_check_launch(FW ? "icv_attention_fwd_framewin" : "icv_attention_fwd_pieces");
+}
+
+// the MFMA shape follows option "attn_mfma" (attention.hip: icv_attn_mfma), as attn7.hip's long-key kernel does
 template <bool UNIT, bool FW = false>
 int launch(const Params& pp, hipStream_t st) {
-  static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW>, LDS_BYTES, &attr_set, "attn7p")) return rc;
-  const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
-  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
-  return icv_check_launch(FW ? "icv_attention_fwd_framewin" : "icv_attention_fwd_pieces");
+  const int mf = icv_attn_mfma(false);
+  if (mf < 0) return 1;
+  return mf == 16 ? launch_mf<UNIT, FW, 16>(pp, st) : launch_mf<UNIT, FW, 32>(pp, st);
 }
 
 }  // namespace att7p

@@ -8,6 +8,7 @@
 #include "icv_common.h"
 
 unsigned long long* icv_attention_trace_buffer(int* capacity);   // attention.hip (icv_attention_trace)
+int icv_attn_mfma(bool short_kv);                                // attention.hip: MFMA shape of attn7 / attn7p (16 or 32; -1 = error set)
 
 namespace attc {
 
@@ -126,6 +127,278 @@ __device__ __forceinline__ void store_result(const Params& p, int64_t qr, int he
         *reinterpret_cast<uint2*>(op + d0 * 32 + rr * 8) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
       }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// MF = 16: the same wave tile (32 query rows x 64 keys) on v_mfma_f32_16x16x32_bf16 (attn7.hip / attn7p.hip, option "attn_mfma").
+// Both kernels run THIS tile, so they stay bit-identical to each other.  Lane maps, g = lane >> 4, t = lane & 15 (restated in plain
+// Python and checked against each other in tests/test_attn_mfma16_layout_cpu.py - change both together):
+//   q-block qb (0, 1):  query row = 16 qb + t;  m_run, l_run, m_base and the reference in the C operand exist once per q-block
+//   Q fragment (B of S^T = K Q^T)   qf[qb][ks][j] = Q[16 qb + t][d = 32 ks + 8 g + j],  ks = 0..3, j = 0..7
+//   K fragment (A), one ds_read_b128:        kf[j] = K[key = 16 kb + t][d = 32 ks + 8 g + j],  kb = 0..3; the K image is the 32 form's
+//                                                    (16-byte chunk c of row `key` sits at chunk c ^ (key & 15)), here c = 4 ks + g
+//   S^T accumulator                 st[kb][qb][r] = S[16 qb + t][key = 16 kb + 4 g + r],  r = 0..3 (the tail mask's key index)
+//   P -> B of O^T += V^T P^T, k-step kk (0, 1):  pf[qb][j] = P[16 qb + t][key = 32 kk + 16 (j >> 2) + 4 g + (j & 3)]: the MFMA's k = 8 g + j
+//   V fragment (A), two ds_read_b64_tr_b16:  vf[j] = V[key = 32 kk + 16 (j >> 2) + 4 g + (j & 3)][d = 16 db + t],  db = 0..7: the SAME
+//                                                    key for (g, j) as pf.  Read jh = j >> 2: lane 4 q + p of a 16-lane group supplies the
+//                                                    address of row 32 kk + 16 jh + 4 g + q, columns 16 db + 4 p ... + 3, and receives
+//                                                    element (t & 3) of the rows q = 0..3 of column group t >> 2 (lds_read_tr16 above)
+//   V image (MF = 16 only):  32-byte segment s (0..7) of row `key` sits at segment s ^ (key & 7).  A 32-lane half of the transposed
+//                            read takes rows 4 g + q, g in {0, 1} or {2, 3}: 8 rows with key & 7 = 0..7 in ONE 32-byte column, which the
+//                            XOR spreads over the 8 segments of the 256-byte bank row (the 32 form's chunk ^ ((key & 3) << 2) image
+//                            would leave rows key and key + 4 on the same banks: 2-way).  The DMA applies it on the source side.
+//   O^T accumulator                 ot[db][qb][r] = O[16 qb + t][d = 16 db + 4 g + r];  the row sum l is four lane-group partials
+// The carried state in memory (acc, ml) and the output are the 32 form's: a chunk written by one shape is read by the other.
+struct Tile16 {
+  f32x4 ot[8][2];
+  float m_run[2], l_run[2], m_base[2];
+  f32x4 cinit[2];     // UNIT: -m_base, the C operand of the first MFMA of every S^T chain
+  bf16x8 qf[2][4];
+};
+
+// softmax state of the wave's two 16-row q-blocks (rows qr_c[qb], clamped): from the carried buffers or empty
+__device__ __forceinline__ void load_state(const Params& p, const int64_t (&qr_c)[2], int head, int g, f32x4 (&ot)[8][2],
+                                           float (&m_run)[2], float (&l_run)[2]) {
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    if (p.state_in) {
+      const float* ap = p.acc + qr_c[qb] * p.ldacc + (int64_t)head * D + 4 * g;
+#pragma unroll
+      for (int db = 0; db < 8; ++db) {
+        const float4 a = *reinterpret_cast<const float4*>(ap + db * 16);
+        ot[db][qb][0] = a.x; ot[db][qb][1] = a.y; ot[db][qb][2] = a.z; ot[db][qb][3] = a.w;
+      }
+      const float2 mlv = *reinterpret_cast<const float2*>(p.ml + (qr_c[qb] * p.heads + head) * 2);
+      m_run[qb] = mlv.x;
+      l_run[qb] = g == 0 ? mlv.y : 0.f;
+    } else {
+#pragma unroll
+      for (int db = 0; db < 8; ++db)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ot[db][qb][r] = 0.f;
+      m_run[qb] = NEG_BIG;
+      l_run[qb] = 0.f;
+    }
+  }
+}
+
+// epilogue of the two q-blocks (rows qr[qb]; a row >= p.Sq is not stored): write the state back, or normalise and store bf16
+__device__ __forceinline__ void store_result(const Params& p, const int64_t (&qr)[2], int head, int g, const f32x4 (&ot)[8][2],
+                                             const float (&m_run)[2], const float (&l_run)[2]) {
+  float l_tot[2];
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    const float l2 = l_run[qb] + __shfl_xor(l_run[qb], 16, 64);
+    l_tot[qb] = l2 + __shfl_xor(l2, 32, 64);
+  }
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    if (qr[qb] >= p.Sq) continue;
+    if (p.state_out == 1) {
+      float* ap = p.acc + qr[qb] * p.ldacc + (int64_t)head * D + 4 * g;
+#pragma unroll
+      for (int db = 0; db < 8; ++db)
+        *reinterpret_cast<float4*>(ap + db * 16) = make_float4(ot[db][qb][0], ot[db][qb][1], ot[db][qb][2], ot[db][qb][3]);
+      if (g == 0) *reinterpret_cast<float2*>(p.ml + (qr[qb] * p.heads + head) * 2) = make_float2(m_run[qb], l_tot[qb]);
+    } else {
+      const float inv = 1.0f / l_tot[qb];
+      bf16_t* op = p.o + qr[qb] * p.ldo + (int64_t)head * D + 4 * g;
+#pragma unroll
+      for (int db = 0; db < 8; ++db) {
+        float a = ot[db][qb][0] * inv, b = ot[db][qb][1] * inv;
+        float c = ot[db][qb][2] * inv, d = ot[db][qb][3] * inv;
+        if (p.state_out == 2) {   // o += result
+          const uint2 prev = *reinterpret_cast<const uint2*>(op + db * 16);
+          a += __uint_as_float(prev.x << 16); b += __uint_as_float(prev.x & 0xFFFF0000u);
+          c += __uint_as_float(prev.y << 16); d += __uint_as_float(prev.y & 0xFFFF0000u);
+        }
+        *reinterpret_cast<uint2*>(op + db * 16) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
+      }
+    }
+  }
+}
+
+// state, reference and Q fragments of a wave whose q-block rows are qr_c[qb] (clamped); issues the Q loads, waits for nothing
+__device__ __forceinline__ void tile16_load_q(const Params& p, const int64_t (&qr_c)[2], int head, int g, Tile16& s) {
+  const bf16_t* qh = p.q + (int64_t)head * D + g * 8;
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) s.qf[qb][ks] = *reinterpret_cast<const bf16x8*>(qh + qr_c[qb] * p.ldq + ks * 32);
+}
+
+template <bool UNIT>
+__device__ __forceinline__ void tile16_init(const Params& p, const int64_t (&qr_c)[2], int head, int g, Tile16& s) {
+  load_state(p, qr_c, head, g, s.ot, s.m_run, s.l_run);
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    s.m_base[qb] = s.m_run[qb] < -1.0e29f ? 0.f : s.m_run[qb];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s.cinit[qb][r] = UNIT ? -s.m_base[qb] : 0.f;
+  }
+}
+
+// source column (elements) of the 16-byte LDS chunk pc of V row `key`: the DMA side of the MF = 16 V image
+__device__ __forceinline__ int tile16_vcol(int pc, int key) { return (pc ^ ((key & 7) << 1)) * 8; }
+
+// one 64-key tile: keys [key0, key0 + 64) of a key axis of skv rows, K image at ks, V image at vs (LDS).  The 32 form's order of work:
+// K reads -> 32 QK^T MFMAs -> per 32-key half: softmax (lazy max, re-base decided on the lane's partial sums), V tr-reads, 16 PV MFMAs.
+// KPREFETCH / DSMAJOR / SETPRIO: attn7.hip's variant bits 2, !32 and 4.
+template <bool UNIT, bool KPREFETCH, bool DSMAJOR, bool SETPRIO>
+__device__ __forceinline__ void tile16(const Params& p, const float p_lim, const char* ks, const char* vs, const int64_t key0,
+                                       const int64_t skv, const int lane, Tile16& s) {
+  const int g = lane >> 4, t = lane & 15;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const int k_row_off = t * 256;
+  const int v_row_off = (4 * g + (t >> 2)) * 256;
+  const int v_sw = (4 * (g & 1) + (t >> 2)) << 5;        // (key & 7) << 5: 32 kk + 16 jh drop out
+  const int v_byte_lo = (t & 3) * 8;
+  f32x4 st[4][2];
+  const bool no_ref = UNIT && (s.m_run[0] < -1.0e29f || s.m_run[1] < -1.0e29f);
+#define T16_KADDR(KB_, KS_) (ks + (KB_) * 4096 + k_row_off + ((((KS_) * 4 + g) ^ t) << 4))
+#define T16_QK(KB_, KS_, KF_)                                                                                       \
+  _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) st[KB_][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(           \
+      KF_, s.qf[qb][KS_], (KS_) == 0 ? (UNIT ? s.cinit[qb] : zero4) : st[KB_][qb], 0, 0, 0)
+  if (KPREFETCH) {
+    bf16x8 kf[4][4];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int kq = 0; kq < 4; ++kq) kf[kb][kq] = *reinterpret_cast<const bf16x8*>(T16_KADDR(kb, kq));
+    __builtin_amdgcn_sched_barrier(0);
+    if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kq = 0; kq < 4; ++kq)
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) { T16_QK(kb, kq, kf[kb][kq]); }
+    if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+  } else if (DSMAJOR) {
+    // software-pipelined by hand, KD fragments ahead, and pinned with sched_group_barrier: left alone, hipcc issues one read, waits
+    // lgkmcnt(0) and issues its two MFMAs - two 16-cycle MFMAs cover a quarter of the read's latency, sixteen times per tile
+    constexpr int KD = 3;
+    bf16x8 kf[16];
+#pragma unroll
+    for (int i = 0; i < KD; ++i) kf[i] = *reinterpret_cast<const bf16x8*>(T16_KADDR(i & 3, i >> 2));
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i + KD < 16) kf[i + KD] = *reinterpret_cast<const bf16x8*>(T16_KADDR((i + KD) & 3, (i + KD) >> 2));
+      T16_QK(i & 3, i >> 2, kf[i]);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, KD, 0);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i + KD < 16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    }
+  } else {
+    if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int kq = 0; kq < 4; ++kq) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(T16_KADDR(kb, kq));
+        T16_QK(kb, kq, kf);
+      }
+    if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+  }
+#undef T16_KADDR
+#undef T16_QK
+  if (key0 + 64 > skv) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t key = key0 + kb * 16 + 4 * g + r;
+        if (key >= skv) { st[kb][0][r] = NEG_BIG; st[kb][1][r] = NEG_BIG; }
+      }
+  }
+  float mb[2] = {-s.m_run[0] * p.sc, -s.m_run[1] * p.sc};
+  float psum[2] = {0.f, 0.f};
+  if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {          // a 32-key half = key blocks 2 kk and 2 kk + 1 = one k-step of the PV MFMAs
+    bf16x8 pf[2];
+    float ps[2];
+#define T16_EXP()                                                                                                   \
+  _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) {                                                                \
+    ps[qb] = 0.f;                                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                 \
+      const float sv = st[2 * kk + (j >> 2)][qb][j & 3];                                                            \
+      const float pv = UNIT ? __builtin_amdgcn_exp2f(sv) : __builtin_amdgcn_exp2f(fmaf(sv, p.sc, mb[qb]));          \
+      ps[qb] += pv;                                                                                                 \
+      pf[qb][j] = (__bf16)pv;                                                                                       \
+    }                                                                                                               \
+  }
+    T16_EXP();
+    // lazy max (attn2.hip): the lane's partial row sum bounds every P it holds
+    if (__any(!(ps[0] <= p_lim) || !(ps[1] <= p_lim) || no_ref)) {
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) {
+        float mloc = st[2 * kk][qb][0];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) mloc = fmaxf(mloc, st[2 * kk + (j >> 2)][qb][j & 3]);
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+        if (UNIT) mloc += s.m_base[qb];                      // st = s - m_base
+        const float m_new = fmaxf(s.m_run[qb], mloc);
+        const float alpha = __builtin_amdgcn_exp2f((s.m_run[qb] - m_new) * p.sc);
+        s.m_run[qb] = m_new;
+        s.l_run[qb] = (s.l_run[qb] + psum[qb]) * alpha;
+        psum[qb] = 0.f;
+#pragma unroll
+        for (int db = 0; db < 8; ++db)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s.ot[db][qb][r] *= alpha;
+        mb[qb] = -m_new * p.sc;
+        if (UNIT) {                                          // re-base this and the later half of the tile, and cinit
+          const float dm = m_new - s.m_base[qb];
+          s.m_base[qb] = m_new;
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb)
+            if (kb >= 2 * kk) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) st[kb][qb][r] -= dm;
+            }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s.cinit[qb][r] = -m_new;
+        }
+      }
+      T16_EXP();
+    }
+#undef T16_EXP
+    psum[0] += ps[0];
+    psum[1] += ps[1];
+    // the V fragments VD d-blocks ahead of their MFMAs, pinned the same way (the next half's exp / convert work floats between them)
+    constexpr int VD = 2;
+    bf16x4 va[8], vb[8];
+#define T16_VREAD(DB_)                                                                                  \
+  {                                                                                                     \
+    const char* va_p = vs + kk * 8192 + v_row_off + (((DB_) * 32 + v_byte_lo) ^ v_sw);                   \
+    va[DB_] = lds_read_tr16(va_p);                                                                      \
+    vb[DB_] = lds_read_tr16(va_p + 4096); /* 16 rows further on: the same key & 7, the same swizzle */ \
+  }
+#pragma unroll
+    for (int db = 0; db < VD; ++db) T16_VREAD(db);
+#pragma unroll
+    for (int db = 0; db < 8; ++db) {
+      if (db + VD < 8) T16_VREAD(db + VD);
+      bf16x8 vf;
+      vf[0] = va[db][0]; vf[1] = va[db][1]; vf[2] = va[db][2]; vf[3] = va[db][3];
+      vf[4] = vb[db][0]; vf[5] = vb[db][1]; vf[6] = vb[db][2]; vf[7] = vb[db][3];
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) s.ot[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb], s.ot[db][qb], 0, 0, 0);
+    }
+#undef T16_VREAD
+    __builtin_amdgcn_sched_group_barrier(0x100, 2 * VD, 0);
+#pragma unroll
+    for (int db = 0; db < 8; ++db) {
+      if (db + VD < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    }
+  }
+  if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+  s.l_run[0] += psum[0];
+  s.l_run[1] += psum[1];
 }
 
 }  // namespace attc
