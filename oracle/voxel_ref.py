@@ -87,7 +87,10 @@ def raycast_dda(vol, vol_min, voxel_size, rays_cam, poses, eps_depth=1e-1, eps_v
         with np.errstate(invalid="ignore"):
             ta = ((F(0.0) - o[:, i]) * inv[:, i]).astype(F)
             tb = ((F(D[i]) - o[:, i]) * inv[:, i]).astype(F)
-        t0 = np.where(z, t0, np.maximum(t0, np.minimum(ta, tb))).astype(F)
+        lo = np.minimum(ta, tb)
+        # fmaxf(t0, lo) with the hardware's -0 < +0: t0 stays +0 when lo is -0 (a ray that starts ON the volume's far face,
+        # (D - o) * inv = 0 * negative).  np.maximum(+0., -0.) may return either zero, so it is spelled as a select here.
+        t0 = np.where(z | ~(lo > t0), t0, lo).astype(F)
         t1 = np.where(z, t1, np.minimum(t1, np.maximum(ta, tb))).astype(F)
     active = ~miss & (t0 < t1)
     c = np.empty((n, 3), np.int64)

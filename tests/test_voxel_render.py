@@ -10,43 +10,7 @@ import pytest
 import torch
 
 from oracle import voxel_ref as V
-
-
-class Cam:
-    def __init__(self, w, h, f):
-        self.w, self.h = w, h
-        u, v = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
-        r = np.stack([(u - w / 2) / f, (v - h / 2) / f, np.ones_like(u)], -1)
-        self.rays = (r / np.linalg.norm(r, axis=-1, keepdims=True)).astype(np.float32)
-
-    def get_rays(self):
-        return torch.from_numpy(self.rays)
-
-
-def _scene(seed=0, n_pts=6000):
-    """Street canyon point cloud in a z-up world: ground, two walls, a few boxes; camera looks along +x."""
-    g = np.random.default_rng(seed)
-    ground = np.stack([g.uniform(0, 30, n_pts), g.uniform(-6, 6, n_pts), g.normal(0, 0.02, n_pts)], 1)
-    wall_l = np.stack([g.uniform(0, 30, n_pts // 2), np.full(n_pts // 2, 6.0) + g.normal(0, 0.03, n_pts // 2), g.uniform(0, 5, n_pts // 2)], 1)
-    wall_r = wall_l * np.array([1, -1, 1])
-    box = np.stack([g.uniform(12, 14, 800), g.uniform(-1, 1, 800), g.uniform(0, 1.5, 800)], 1)
-    thin = np.stack([np.full(60, 8.03), g.uniform(-0.5, 0.5, 60), g.uniform(0.5, 1.0, 60)], 1)     # a one-voxel-thick sheet (eps cases)
-    pts = np.concatenate([ground, wall_l, wall_r, box, thin]).astype(np.float32)
-    sem = np.concatenate([np.full(len(ground), 18), np.full(len(wall_l) * 2, 14), np.full(len(box), 1), np.full(len(thin), 10)]).astype(np.int32)
-    sem[g.integers(0, len(sem), 200)] = 15                      # label noise: exercises the per-voxel mode
-    inst = np.where(sem == 1, 7, 0).astype(np.int32)
-    return pts, sem, inst
-
-
-def _poses(n):
-    # camera (x right, y down, z front) -> world (x front, y left, z up), moving forward, slight yaw
-    base = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 1.6], [0, 0, 0, 1]], np.float32)
-    out = []
-    for i in range(n):
-        yaw = 0.05 * i
-        rz = np.array([[np.cos(yaw), -np.sin(yaw), 0, 1.0 + 0.7 * i], [np.sin(yaw), np.cos(yaw), 0, 0.1 * i], [0, 0, 1, 0], [0, 0, 0, 1]], np.float32)
-        out.append(rz @ base)
-    return np.stack(out).astype(np.float32)
+from voxel_cases import Cam, _poses, _scene
 
 
 def test_voxelisation_mode_and_rounding():
