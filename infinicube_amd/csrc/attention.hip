@@ -147,6 +147,22 @@ int icv_attn_mfma(bool short_kv) {
   return -1;
 }
 
+// Body of the MF = 16 tile attc::tile16 (icv_set_option("attn_tile16_lean", n)): 1 = the lean body (K / V fragment addresses formed once per
+// work-group and moved with the ring, scalar row sums, the "no reference yet" test folded into the lazy-max limit), 0 = the first body,
+// negative = the default.  Same arithmetic in the same order: outputs and carried state are bit-identical (tests/test_attn_lean_tile_gpu.py).
+// Read HERE by attn7.hip and attn7p.hip, so the long-key launches always agree; the short-key shape has a default of its own.
+// Defaults: 1 for both - every round of the lean arm beat every round of the first body's at the 14B self-attention (22.13 vs 23.29 ms),
+// its two shard shapes and the 512-key cross-attention (interleaved in one process, tools/attn_lean_ab.py; profiles/attn_lean_tile/README.md).
+constexpr int ATTN_TILE16_LEAN_DEFAULT = 1;
+constexpr int ATTN_TILE16_LEAN_SHORT_DEFAULT = 1;
+int icv_attn_tile16_lean(bool short_kv) {
+  const int v = icv_get_option_int("attn_tile16_lean", -1);
+  if (v < 0) return short_kv ? ATTN_TILE16_LEAN_SHORT_DEFAULT : ATTN_TILE16_LEAN_DEFAULT;
+  if (v == 0 || v == 1) return v;
+  icv_set_error("attn_tile16_lean = %d: 1 = the lean body of the 16x16x32 tile, 0 = the first body; negative = the default", v);
+  return -1;
+}
+
 // ---- diagnostics: where and when every work-group of the NEXT attn7 launches runs -----------------------------------------
 // icv_attention_trace(buf, capacity): buf = device u64 [capacity][4] (NULL switches tracing off).  While set, every attn7
 // work-group b < capacity writes buf[b] = {start, end (s_memrealtime ticks, 100 MHz), HW_ID, XCC_ID} - the round structure and

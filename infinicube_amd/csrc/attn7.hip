@@ -13,6 +13,7 @@
 // the same 16 ds_read_b128 and 32 ds_read_b64_tr_b16, a V image swizzled by (key & 7) - through attc::tile16 (attn_common.h: lane maps,
 // fragment prefetch), which attn7p.hip runs too.  Under the power limit the shape costs less energy per FLOP: 2.5 % of the 14B
 // self-attention launch, 5 % of the 512-key cross-attention (profiles/attn_mfma16/README.md).
+#include <type_traits>
 #include "attn_common.h"
 
 namespace att7 {
@@ -73,9 +74,11 @@ __device__ __forceinline__ void dma16s(const void* base, unsigned off, unsigned 
 // MF (option "attn_mfma"): 32 = v_mfma_f32_32x32x16_bf16, the body below; 16 = v_mfma_f32_16x16x32_bf16 at the same wave tile, ring and
 // softmax: attc::tile16 and its lane maps in attn_common.h (a lane then carries TWO query rows, q and q + 16; the V image's swizzle
 // differs, see there), shared with attn7p.hip so that the two kernels stay bit-identical at either shape.
-template <int VAR, int NW, int NST, int MF>
+// LEAN (MF = 16 only, option "attn_tile16_lean", default on): attc::tile16's lean body - K / V fragment addresses formed once and moved with the ring
+template <int VAR, int NW, int NST, int MF, bool LEAN = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7_kernel(Params p) {
   static_assert(MF == 16 || MF == 32, "MF: 16 (16x16x32 MFMAs) or 32 (32x32x16)");
+  static_assert(MF == 16 || !LEAN, "the lean body is a body of the MF = 16 tile");
   constexpr bool STAGGER = VAR & 1, KPREFETCH = VAR & 2, SETPRIO = VAR & 4, DEEP = VAR & 8, UNIT = VAR & 16;
   // QK^T MFMA order: d-step major (consecutive MFMAs share the Q fragment: less operand toggling, +0.6...1.4 % under the power
   // cap, profiles/r02/attention_variants.md) unless bit 32 asks for round 1's key-block-major order
@@ -223,10 +226,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   const int ahead = 2 + grp + (DEEP ? 1 : 0);   // group 1 runs one tile behind, so its DMA duties are one tile further ahead
 
   // one 64-key tile: K reads -> 16 QK^T MFMAs -> softmax -> V tr-reads -> 16 PV MFMAs (no DMA, no waits)
-  auto tile = [&](const int t) __attribute__((always_inline)) {
+  // par: the tile's place in a step of two stages, as a std::integral_constant (the paired schedule: 0 and 1; the others: always 0).
+  // LEAN: la16 points at the stage of the step's first tile; LA16_NEXT moves it on behind the step.
+  attc::Tile16Addr la16;
+  if constexpr (LEAN) {
+    attc::tile16_lean_addr(lds_base, lane, la16);
+    attc::tile16_lean_lim<UNIT>(s16, p_lim, la16);
+  }
+#define A7_LA16_NEXT(T_, N_)                                                                                                       \
+  do {                                                                                                                             \
+    if constexpr (LEAN) attc::tile16_lean_advance(la16, (((T_) + (N_)) & (NST - 1)) == 0 ? ((N_) - NST) * STAGE_BYTES : (N_) * STAGE_BYTES); \
+  } while (0)
+  auto tile = [&](const auto par, const int t) __attribute__((always_inline)) {
+    const int64_t key0 = (int64_t)t * KVB;
+    if constexpr (LEAN) {
+      attc::tile16<UNIT, KPREFETCH, DSMAJOR, SETPRIO, true, decltype(par)::value>(p, p_lim, nullptr, nullptr, key0, p.Skv, lane, s16, &la16);
+      return;
+    }
     const char* ks = smem + (t & (NST - 1)) * STAGE_BYTES;
     const char* vs = ks + TILE_BYTES;
-    const int64_t key0 = (int64_t)t * KVB;
     if constexpr (MF == 16) {
       attc::tile16<UNIT, KPREFETCH, DSMAJOR, SETPRIO>(p, p_lim, ks, vs, key0, p.Skv, lane, s16);
       return;
@@ -358,7 +376,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     // two-stage ring: tile t+1 was requested one interval ago; its stage is re-requested (tile t+2 -> stage t % 2) right
     // after the barrier that ends the last read of tile t
     for (int t = 0; t < nt; ++t) {
-      tile(t);
+      tile(std::integral_constant<int, 0>{}, t);
+      A7_LA16_NEXT(t, 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       A7_BARRIER();
       A7_DMA_TILE(t + 2);
@@ -369,8 +388,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
         A7_DMA_TILE(t + 2);
         A7_DMA_TILE(t + 3);
       }
-      tile(t);
-      if (t + 1 < nt) tile(t + 1);
+      tile(std::integral_constant<int, 0>{}, t);
+      if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, t + 1);
+      A7_LA16_NEXT(t, 2);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // issued a whole 128-key interval ago
       if (!(p.ablate & 2)) A7_BARRIER();
     }
@@ -378,7 +398,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     for (int t = 0; t < nt; ++t) {
       // DMA of tile t+ahead first (longest possible flight), counted wait at the end of the interval
       if (!(p.ablate & 1)) A7_DMA_TILE(t + ahead);
-      tile(t);
+      tile(std::integral_constant<int, 0>{}, t);
+      A7_LA16_NEXT(t, 1);
       A7_VMCNT4();    // this wave's share of tile t+ahead-1 has landed (tile t+ahead may still be in flight)
       if (!(p.ablate & 2)) A7_BARRIER();   // ... and is published to the block
     }
@@ -401,21 +422,24 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     unsigned long long* t = p.trace + (size_t)blockIdx.x * 4;
     t[0] = t_start; t[1] = __builtin_amdgcn_s_memrealtime(); t[2] = hwid; t[3] = xcc;
   }
+#undef A7_LA16_NEXT
 }
 
-template <int VAR, int NW, int NST, int MF>
+template <int VAR, int NW, int NST, int MF, bool LEAN = false>
 int launch_mf(const Params& p, hipStream_t st) {
   constexpr int LDS_BYTES = NST * STAGE_BYTES;   // 128 KiB (one block per CU) or 64 KiB (two)
   static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7_kernel<VAR, NW, NST, MF>, LDS_BYTES, &attr_set, "attn7")) return rc;
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7_kernel<VAR, NW, NST, MF, LEAN>, LDS_BYTES, &attr_set, "attn7")) return rc;
   const int64_t nwg = (int64_t)p.heads * p.nqb;
-  hipLaunchKernelGGL((attn7_kernel<VAR, NW, NST, MF>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, p);
+  hipLaunchKernelGGL((attn7_kernel<VAR, NW, NST, MF, LEAN>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, p);
   return icv_check_launch("icv_attention(7)");
 }
 
+// mf: the MFMA shape; lean: the body of the MF = 16 tile (options "attn_mfma", "attn_tile16_lean")
 template <int VAR, int NW = 8, int NST = 4>
-int launch(const Params& p, hipStream_t st, int mf) {
-  return mf == 16 ? launch_mf<VAR, NW, NST, 16>(p, st) : launch_mf<VAR, NW, NST, 32>(p, st);
+int launch(const Params& p, hipStream_t st, int mf, int lean) {
+  if (mf != 16) return launch_mf<VAR, NW, NST, 32>(p, st);
+  return lean ? launch_mf<VAR, NW, NST, 16, true>(p, st) : launch_mf<VAR, NW, NST, 16>(p, st);
 }
 
 }  // namespace att7
@@ -437,28 +461,30 @@ int icv_attn7_dispatch(const void* q, int64_t ldq, const void* k, int64_t ldk, c
   // MFMA shape (option "attn_mfma"): the long-key kernel always follows attn7p.hip; the short-key shape has its own default
   const int mf = icv_attn_mfma(short_kv);
   if (mf < 0) return 1;
-  if (short_kv) return (var & 16) ? att7::launch<16, 4, 2>(p, st, mf) : att7::launch<0, 4, 2>(p, st, mf);
+  const int lean = mf == 16 ? icv_attn_tile16_lean(short_kv) : 0;
+  if (lean < 0) return 1;
+  if (short_kv) return (var & 16) ? att7::launch<16, 4, 2>(p, st, mf, lean) : att7::launch<0, 4, 2>(p, st, mf, lean);
   switch (var) {
-    case 0: return att7::launch<0>(p, st, mf);
-    case 1: return att7::launch<1>(p, st, mf);
-    case 4: return att7::launch<4>(p, st, mf);
-    case 5: return att7::launch<5>(p, st, mf);
-    case 6: return att7::launch<6>(p, st, mf);
-    case 7: return att7::launch<7>(p, st, mf);
-    case 8: return att7::launch<8>(p, st, mf);
-    case 24: return att7::launch<24>(p, st, mf);
-    case 32: return att7::launch<32>(p, st, mf);
-    case 48: return att7::launch<48>(p, st, mf);
-    case 128: return att7::launch<128>(p, st, mf);
-    case 144: return att7::launch<144>(p, st, mf);
-    case 132: return att7::launch<132>(p, st, mf);
-    case 148: return att7::launch<148>(p, st, mf);
-    case 16: return att7::launch<16>(p, st, mf);
-    case 17: return att7::launch<17>(p, st, mf);
-    case 20: return att7::launch<20>(p, st, mf);
-    case 21: return att7::launch<21>(p, st, mf);
-    case 22: return att7::launch<22>(p, st, mf);
-    case 23: return att7::launch<23>(p, st, mf);
+    case 0: return att7::launch<0>(p, st, mf, lean);
+    case 1: return att7::launch<1>(p, st, mf, lean);
+    case 4: return att7::launch<4>(p, st, mf, lean);
+    case 5: return att7::launch<5>(p, st, mf, lean);
+    case 6: return att7::launch<6>(p, st, mf, lean);
+    case 7: return att7::launch<7>(p, st, mf, lean);
+    case 8: return att7::launch<8>(p, st, mf, lean);
+    case 24: return att7::launch<24>(p, st, mf, lean);
+    case 32: return att7::launch<32>(p, st, mf, lean);
+    case 48: return att7::launch<48>(p, st, mf, lean);
+    case 128: return att7::launch<128>(p, st, mf, lean);
+    case 144: return att7::launch<144>(p, st, mf, lean);
+    case 132: return att7::launch<132>(p, st, mf, lean);
+    case 148: return att7::launch<148>(p, st, mf, lean);
+    case 16: return att7::launch<16>(p, st, mf, lean);
+    case 17: return att7::launch<17>(p, st, mf, lean);
+    case 20: return att7::launch<20>(p, st, mf, lean);
+    case 21: return att7::launch<21>(p, st, mf, lean);
+    case 22: return att7::launch<22>(p, st, mf, lean);
+    case 23: return att7::launch<23>(p, st, mf, lean);
   }
   icv_set_error("icv_attention_fwd: unknown attn7 variant %d", var);
   return 1;

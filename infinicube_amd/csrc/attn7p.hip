@@ -33,6 +33,7 @@
 // is one format for both.  22.60 vs 23.17 ms at the 14B self-attention (profiles/attn_mfma16/README.md).
 // Replaces: the chunked icv_attention_fwd_chunk sequence of the sequence-parallel self-attention (the fork's / xDiT-USP's gather-then-
 // flash_attention [EXT]); the reference itself has no such path (one GPU, [R infinicube/inference/guidance_buffer_generation.py:759-766]).
+#include <type_traits>
 #include "attn_common.h"
 
 namespace att7p {
@@ -105,9 +106,11 @@ __device__ __forceinline__ unsigned load_flag_async(const unsigned* f) {
 // FW: the frame-windowed instantiation (see the head of this file)
 // MF (option "attn_mfma"): 32 = v_mfma_f32_32x32x16_bf16, the tile below; 16 = v_mfma_f32_16x16x32_bf16 at the same wave tile, ring and
 // softmax: attc::tile16 (attn_common.h, lane maps there), the tile attn7.hip runs at MF = 16 - the two stay bit-identical at either shape
-template <bool UNIT, bool FW, int MF>
+// LEAN (MF = 16 only, option "attn_tile16_lean", default on): attc::tile16's lean body - K / V fragment addresses formed once and moved with the ring
+template <bool UNIT, bool FW, int MF, bool LEAN = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7p_kernel(Params pp) {
   static_assert(MF == 16 || MF == 32, "MF: 16 (16x16x32 MFMAs) or 32 (32x32x16)");
+  static_assert(MF == 16 || !LEAN, "the lean body is a body of the MF = 16 tile");
   const attc::Params& p = pp.a;
   const float p_lim = __builtin_amdgcn_exp2f(p.thr);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -271,7 +274,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   const int v_sw = (t16 >> 2) << 6;
 
   // one 64-key tile from ring stage `stg`: keys [key0, key0 + 64) of a piece with `skv` rows (attn7.hip's tile, variant 148 / 132)
-  auto tile = [&](const int stg, const int key0, const int skv) __attribute__((always_inline)) {
+  // par: stg's parity as a std::integral_constant (an interval takes an even and an odd stage per barrier).  LEAN: la16 points at
+  // the even stage of the interval's half of the ring and is moved to the other half once per interval.
+  attc::Tile16Addr la16;
+  int la16_step = 2 * STAGE_BYTES;
+  if constexpr (LEAN) {
+    attc::tile16_lean_addr(lds_base, lane, la16);
+    attc::tile16_lean_lim<UNIT>(s16, p_lim, la16);
+  }
+  auto tile = [&](const auto par, const int stg, const int key0, const int skv) __attribute__((always_inline)) {
+    if constexpr (LEAN) {
+      attc::tile16<UNIT, false, true, true, true, decltype(par)::value>(p, p_lim, nullptr, nullptr, key0, skv, lane, s16, &la16);
+      return;
+    }
     const char* ks = smem + (stg & (NST - 1)) * STAGE_BYTES;
     const char* vs = ks + TILE_BYTES;
     if constexpr (MF == 16) {
@@ -405,8 +420,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
       const bool poll = has_next && !next_ready;         // wave-uniform
       unsigned fv = 0;
       if (poll && wave == 0) fv = load_flag_async(pp.flags + nflag);
-      tile((int)(gt + t), t * KVB, skv);
-      if (t + 1 < nt) tile((int)(gt + t + 1), (t + 1) * KVB, skv);
+      tile(std::integral_constant<int, 0>{}, (int)(gt + t), t * KVB, skv);
+      if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, (int)(gt + t + 1), (t + 1) * KVB, skv);
+      if constexpr (LEAN) {                              // the next interval reads the other half: gt + t is 2 (mod 4) further on
+        attc::tile16_lean_advance(la16, la16_step);
+        la16_step = -la16_step;
+      }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this interval's DMA requests and the flag sample
       if (poll && tid == 0) verdict[iv & 1] = (int)(fv - nvalue) >= 0 ? 1u : 0u;
       P_BARRIER();
@@ -454,12 +473,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #undef P_WAIT_PIECE
 }
 
-template <bool UNIT, bool FW, int MF>
+template <bool UNIT, bool FW, int MF, bool LEAN = false>
 int launch_mf(const Params& pp, hipStream_t st) {
   static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW, MF>, LDS_BYTES, &attr_set, "attn7p")) return rc;
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW, MF, LEAN>, LDS_BYTES, &attr_set, "attn7p")) return rc;
   const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
-  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW, MF>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
+  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW, MF, LEAN>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
   return icv_check_launch(FW ? "icv_attention_fwd_framewin" : "icv_attention_fwd_pieces");
 }
 
@@ -468,7 +487,10 @@ template <bool UNIT, bool FW = false>
 int launch(const Params& pp, hipStream_t st) {
   const int mf = icv_attn_mfma(false);
   if (mf < 0) return 1;
-  return mf == 16 ? launch_mf<UNIT, FW, 16>(pp, st) : launch_mf<UNIT, FW, 32>(pp, st);
+  if (mf != 16) return launch_mf<UNIT, FW, 32>(pp, st);
+  const int lean = icv_attn_tile16_lean(false);     // body of the MF = 16 tile (option "attn_tile16_lean")
+  if (lean < 0) return 1;
+  return lean ? launch_mf<UNIT, FW, 16, true>(pp, st) : launch_mf<UNIT, FW, 16>(pp, st);
 }
 
 }  // namespace att7p

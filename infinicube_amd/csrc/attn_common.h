@@ -9,6 +9,7 @@
 
 unsigned long long* icv_attention_trace_buffer(int* capacity);   // attention.hip (icv_attention_trace)
 int icv_attn_mfma(bool short_kv);                                // attention.hip: MFMA shape of attn7 / attn7p (16 or 32; -1 = error set)
+int icv_attn_tile16_lean(bool short_kv);                         // attention.hip: body of the MF = 16 tile (1 = lean, 0 = the first one)
 
 namespace attc {
 
@@ -241,12 +242,59 @@ __device__ __forceinline__ void tile16_init(const Params& p, const int64_t (&qr_
 // source column (elements) of the 16-byte LDS chunk pc of V row `key`: the DMA side of the MF = 16 V image
 __device__ __forceinline__ int tile16_vcol(int pc, int key) { return (pc ^ ((key & 7) << 1)) * 8; }
 
+// LEAN body of the tile (option "attn_tile16_lean"; profiles/attn_lean_tile/README.md): the same arithmetic in the same order, with less
+// vector work that is not softmax.  The per-lane K / V fragment addresses (one per d-step of K, one per d-block of V) are formed ONCE per
+// work-group and FOLLOW the ring: the kernel moves them on by a wave-uniform byte count when it moves to another part of the ring (12
+// adds per step) instead of adding a fresh stage base to per-lane constants in every 32-key half.  What is known at compile time - the
+// tile's place STG (0, 1) inside a step of two stages, kb * 4096, kk * 8192, + 4096 - sits in the offset: field of the ds_reads.  The
+// lane's two row sums stay two scalar chains (hipcc's SLP vectoriser otherwise packs them into v_pk_add_f32, which is slow beside MFMAs),
+// and the first body's per-tile "no reference yet" compares are state (Tile16Addr::lim).  22.13 vs 23.29 ms at the 14B self-attention.
+typedef __attribute__((address_space(3))) bf16x8 lds_bf16x8;
+struct Tile16Addr {               // the lean body's own per-lane state
+  unsigned k[4], v[8];             // LDS byte addresses of this lane's fragments in the K image / the V image of the current stage
+  // UNIT: the lazy-max test's limit on the lane's partial row sum of q-block qb, with "this q-block has no reference yet" folded in: -1
+  // (no sum of P is <= -1, so the test fires) while m_run was empty when the CURRENT tile began, p_lim after that.  The first body
+  // evaluates that condition at the top of every tile; here it is state, renewed where m_run changes for the last time in a tile.
+  float lim[2];
+};
+template <bool UNIT>
+__device__ __forceinline__ void tile16_lean_lim(const Tile16& s, const float p_lim, Tile16Addr& a) {
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) a.lim[qb] = UNIT && s.m_run[qb] < -1.0e29f ? -1.0f : p_lim;
+}
+__device__ __forceinline__ void tile16_lean_addr(const unsigned lds_base, const int lane, Tile16Addr& a) {
+  const int g = lane >> 4, t = lane & 15;
+  const int v_row_off = (4 * g + (t >> 2)) * 256;
+  const int v_sw = (4 * (g & 1) + (t >> 2)) << 5;
+  const int v_byte_lo = (t & 3) * 8;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) a.k[ks] = lds_base + t * 256 + (((ks * 4 + g) ^ t) << 4);
+#pragma unroll
+  for (int db = 0; db < 8; ++db) a.v[db] = lds_base + 16384 + v_row_off + ((db * 32 + v_byte_lo) ^ v_sw);
+}
+// move the addresses on by `bytes` (wave-uniform, may be negative: the ring wraps)
+__device__ __forceinline__ void tile16_lean_advance(Tile16Addr& a, const int bytes) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) a.k[ks] += (unsigned)bytes;
+#pragma unroll
+  for (int db = 0; db < 8; ++db) a.v[db] += (unsigned)bytes;
+}
+
+// a + b as fma(b, one, a), one = 1.0 the compiler cannot see through: one rounding of the exact sum, so the SAME bits as a + b, but not an
+// fadd - the lane's two row-sum chains are isomorphic, and the SLP vectoriser packs two fadd chains into v_pk_add_f32, which cost more
+// beside MFMAs than scalar adds.  The first chain stays plain C++ (alone it has nothing to pair with).  Not inline assembly: the
+// compiler must see the instruction to keep the wait state between a v_exp_f32 and its consumer.
+__device__ __forceinline__ float t16_add_opaque(const float a, const float b, const float one) { return __builtin_fmaf(b, one, a); }
+
 // one 64-key tile: keys [key0, key0 + 64) of a key axis of skv rows, K image at ks, V image at vs (LDS).  The 32 form's order of work:
 // K reads -> 32 QK^T MFMAs -> per 32-key half: softmax (lazy max, re-base decided on the lane's partial sums), V tr-reads, 16 PV MFMAs.
 // KPREFETCH / DSMAJOR / SETPRIO: attn7.hip's variant bits 2, !32 and 4.
-template <bool UNIT, bool KPREFETCH, bool DSMAJOR, bool SETPRIO>
+// LEAN: the tile lies STG stages (32 KiB each) past the one the addresses `la` point at; ks / vs are not used.
+template <bool UNIT, bool KPREFETCH, bool DSMAJOR, bool SETPRIO, bool LEAN = false, int STG = 0>
 __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const char* ks, const char* vs, const int64_t key0,
-                                       const int64_t skv, const int lane, Tile16& s) {
+                                       const int64_t skv, const int lane, Tile16& s, Tile16Addr* la = nullptr) {
+  static_assert(STG == 0 || (LEAN && STG == 1), "STG: the tile's place in a step of two stages (lean body only)");
+  static_assert(STG * 32768 + 8192 + 4096 < 65536, "the ds_read offset: field holds 16 bits");
   const int g = lane >> 4, t = lane & 15;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int k_row_off = t * 256;
@@ -254,8 +302,13 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
   const int v_sw = (4 * (g & 1) + (t >> 2)) << 5;        // (key & 7) << 5: 32 kk + 16 jh drop out
   const int v_byte_lo = (t & 3) * 8;
   f32x4 st[4][2];
-  const bool no_ref = UNIT && (s.m_run[0] < -1.0e29f || s.m_run[1] < -1.0e29f);
+  const bool no_ref = UNIT && !LEAN && (s.m_run[0] < -1.0e29f || s.m_run[1] < -1.0e29f);     // LEAN: folded into la->lim
 #define T16_KADDR(KB_, KS_) (ks + (KB_) * 4096 + k_row_off + ((((KS_) * 4 + g) ^ t) << 4))
+#define T16_KLOAD(DST_, KB_, KS_)                                                                                   \
+  do {                                                                                                              \
+    if constexpr (LEAN) DST_ = *(const lds_bf16x8*)(la->k[KS_] + (unsigned)(STG * 32768 + (KB_) * 4096));           \
+    else DST_ = *reinterpret_cast<const bf16x8*>(T16_KADDR(KB_, KS_));                                              \
+  } while (0)
 #define T16_QK(KB_, KS_, KF_)                                                                                       \
   _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) st[KB_][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(           \
       KF_, s.qf[qb][KS_], (KS_) == 0 ? (UNIT ? s.cinit[qb] : zero4) : st[KB_][qb], 0, 0, 0)
@@ -264,7 +317,7 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-      for (int kq = 0; kq < 4; ++kq) kf[kb][kq] = *reinterpret_cast<const bf16x8*>(T16_KADDR(kb, kq));
+      for (int kq = 0; kq < 4; ++kq) T16_KLOAD(kf[kb][kq], kb, kq);
     __builtin_amdgcn_sched_barrier(0);
     if (SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -278,10 +331,10 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
     constexpr int KD = 3;
     bf16x8 kf[16];
 #pragma unroll
-    for (int i = 0; i < KD; ++i) kf[i] = *reinterpret_cast<const bf16x8*>(T16_KADDR(i & 3, i >> 2));
+    for (int i = 0; i < KD; ++i) T16_KLOAD(kf[i], i & 3, i >> 2);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      if (i + KD < 16) kf[i + KD] = *reinterpret_cast<const bf16x8*>(T16_KADDR((i + KD) & 3, (i + KD) >> 2));
+      if (i + KD < 16) T16_KLOAD(kf[i + KD], (i + KD) & 3, (i + KD) >> 2);
       T16_QK(i & 3, i >> 2, kf[i]);
     }
     __builtin_amdgcn_sched_group_barrier(0x100, KD, 0);
@@ -296,12 +349,14 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int kq = 0; kq < 4; ++kq) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(T16_KADDR(kb, kq));
+        bf16x8 kf;
+        T16_KLOAD(kf, kb, kq);
         T16_QK(kb, kq, kf);
       }
     if (SETPRIO) __builtin_amdgcn_s_setprio(0);
   }
 #undef T16_KADDR
+#undef T16_KLOAD
 #undef T16_QK
   if (key0 + 64 > skv) {
 #pragma unroll
@@ -312,6 +367,8 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
         if (key >= skv) { st[kb][0][r] = NEG_BIG; st[kb][1][r] = NEG_BIG; }
       }
   }
+  float one = 1.0f;                          // LEAN: see t16_add_opaque
+  if (LEAN) asm("" : "+s"(one));
   float mb[2] = {-s.m_run[0] * p.sc, -s.m_run[1] * p.sc};
   float psum[2] = {0.f, 0.f};
   if (SETPRIO) __builtin_amdgcn_s_setprio(1);
@@ -325,13 +382,15 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
     _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                 \
       const float sv = st[2 * kk + (j >> 2)][qb][j & 3];                                                            \
       const float pv = UNIT ? __builtin_amdgcn_exp2f(sv) : __builtin_amdgcn_exp2f(fmaf(sv, p.sc, mb[qb]));          \
-      ps[qb] += pv;                                                                                                 \
+      if (LEAN && j == 0) ps[qb] = pv; /* 0 + pv, exactly */                                                        \
+      else if (LEAN && qb == 1) ps[qb] = t16_add_opaque(ps[qb], pv, one);                                           \
+      else ps[qb] += pv;                                                                                            \
       pf[qb][j] = (__bf16)pv;                                                                                       \
     }                                                                                                               \
   }
     T16_EXP();
     // lazy max (attn2.hip): the lane's partial row sum bounds every P it holds
-    if (__any(!(ps[0] <= p_lim) || !(ps[1] <= p_lim) || no_ref)) {
+    if (__any(LEAN && UNIT ? !(ps[0] <= la->lim[0]) || !(ps[1] <= la->lim[1]) : !(ps[0] <= p_lim) || !(ps[1] <= p_lim) || no_ref)) {
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
         float mloc = st[2 * kk][qb][0];
@@ -343,6 +402,8 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
         const float m_new = fmaxf(s.m_run[qb], mloc);
         const float alpha = __builtin_amdgcn_exp2f((s.m_run[qb] - m_new) * p.sc);
         s.m_run[qb] = m_new;
+        // an empty m_run at the top of the tile forces the re-base in BOTH halves (as no_ref does), so the second half's sees the final one
+        if (LEAN && UNIT && kk == 1) la->lim[qb] = m_new < -1.0e29f ? -1.0f : p_lim;
         s.l_run[qb] = (s.l_run[qb] + psum[qb]) * alpha;
         psum[qb] = 0.f;
 #pragma unroll
@@ -366,16 +427,27 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
       T16_EXP();
     }
 #undef T16_EXP
-    psum[0] += ps[0];
-    psum[1] += ps[1];
+    if (LEAN) {                              // ps >= +0, so 0 + ps = ps exactly
+      psum[0] = kk == 0 ? ps[0] : psum[0] + ps[0];
+      psum[1] = kk == 0 ? ps[1] : t16_add_opaque(psum[1], ps[1], one);
+    } else {
+      psum[0] += ps[0];
+      psum[1] += ps[1];
+    }
     // the V fragments VD d-blocks ahead of their MFMAs, pinned the same way (the next half's exp / convert work floats between them)
     constexpr int VD = 2;
     bf16x4 va[8], vb[8];
 #define T16_VREAD(DB_)                                                                                  \
   {                                                                                                     \
-    const char* va_p = vs + kk * 8192 + v_row_off + (((DB_) * 32 + v_byte_lo) ^ v_sw);                   \
-    va[DB_] = lds_read_tr16(va_p);                                                                      \
-    vb[DB_] = lds_read_tr16(va_p + 4096); /* 16 rows further on: the same key & 7, the same swizzle */ \
+    if constexpr (LEAN) {                                                                               \
+      const unsigned va_a = la->v[DB_] + (unsigned)(STG * 32768 + kk * 8192);                           \
+      va[DB_] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va_a))); \
+      vb[DB_] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va_a + 4096u))); \
+    } else {                                                                                            \
+      const char* va_p = vs + kk * 8192 + v_row_off + (((DB_) * 32 + v_byte_lo) ^ v_sw);                 \
+      va[DB_] = lds_read_tr16(va_p);                                                                    \
+      vb[DB_] = lds_read_tr16(va_p + 4096); /* 16 rows further on: the same key & 7, the same swizzle */ \
+    }                                                                                                   \
   }
 #pragma unroll
     for (int db = 0; db < VD; ++db) T16_VREAD(db);
@@ -398,7 +470,8 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
   }
   if (SETPRIO) __builtin_amdgcn_s_setprio(0);
   s.l_run[0] += psum[0];
-  s.l_run[1] += psum[1];
+  if (LEAN) s.l_run[1] = t16_add_opaque(s.l_run[1], psum[1], one);
+  else s.l_run[1] += psum[1];
 }
 
 }  // namespace attc
