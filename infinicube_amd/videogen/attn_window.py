@@ -26,16 +26,6 @@ import numpy as np
 ENV_WINDOW, ENV_SINK = "ICV_ATTN_WINDOW_FRAMES", "ICV_ATTN_SINK_FRAMES"
 
 
-def env_int(name: str, value: Optional[str]) -> Optional[int]:
-    """The value of an ICV_ATTN_*_FRAMES variable -> int (unset / "" -> None); anything but an integer raises ValueError."""
-    if value is None or value == "":
-        return None
-    try:
-        return int(value)
-    except ValueError:
-        raise ValueError(f"{name} must be an integer number of latent frames, got {value!r}") from None
-
-
 def validate(window, sink, T: Optional[int] = None) -> Optional[Tuple[int, int]]:
     """(window, sink) as ints - sink clamped to the clip's ``T`` latent frames when T is given - or None when the setting is off
     (window None and no sink).  Negatives, non-integers and a sink without a window raise ValueError."""

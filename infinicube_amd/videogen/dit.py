@@ -42,6 +42,7 @@ from typing import Dict, Optional
 import torch
 
 from ..native import CFG_ZERO_WORKSPACE_DOUBLES
+from . import options
 from .config import TokenGrid, WanDiTConfig
 from .ops import BF16, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32, F32, FP8, RopeTable
 from .scheduler import FlowMatchScheduler
@@ -615,10 +616,9 @@ class WanDiT:
         grid = getattr(self, "grid", None)
         if aw is None or grid is None or attn_window.dense(grid.T, aw[0]):
             return None
-        if self.sp_on:
-            raise ValueError("attention_window_frames cannot be combined with sequence parallelism (world > 1) yet")
-        if self.attn_fp8:
-            raise ValueError("attention_window_frames cannot be combined with the e4m3 self-attention mode (attn_dtype='fp8') yet")
+        options.check_scope({options.ATTN_WINDOW: "attention_window_frames"},
+                            {options.PARALLEL: self.sp_on and "sequence parallelism (world > 1)",
+                             options.FP8_ATTN: self.attn_fp8 and "the e4m3 self-attention mode (attn_dtype='fp8')"})
         return aw[0], min(aw[1], grid.T)
 
     def _native_eligible(self) -> bool:
@@ -1164,29 +1164,24 @@ class WanDiT:
         The scales are read back once, after the loop, into ``self.guidance_scales``.  None: today's launches, allocations and bits."""
         ops, plan = self.ops, self.plan
         self.guidance_scales = None
-        if guidance is not None:
-            for on, what in ((sliding_window is not None and len(sliding_window.windows) > 1, "more than one sliding temporal window"),
-                             (self.sp_on or plan.world > 1 or branch_exchange is not None,
-                              "sequence / CFG-branch parallelism (world > 1): the moments would need an all-reduce")):
-                if on:
-                    raise ValueError(f"cfg_zero_star / cfg_zero_init_steps cannot be combined with {what} yet")
-            if guidance.optimized_scale and not (ctx_uncond is not None and cfg_scale != 1.0):
-                raise ValueError("cfg_zero_star needs classifier-free guidance (an unconditional context and cfg_scale != 1)")
-        if solver is not None:
-            for on, what in ((sliding_window is not None and len(sliding_window.windows) > 1, "more than one sliding temporal window"),
-                             (self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)")):
-                if on:
-                    raise ValueError(f"sample_solver={solver.name!r} cannot be combined with {what} yet")
-            if len(solver.sigmas) != len(scheduler.sigmas) or any(a != b for a, b in zip(solver.sigmas, scheduler.sigmas)):
-                raise ValueError("denoise: the solver plan was not built on this scheduler's sigmas")
-        if sliding_window is not None and len(sliding_window.windows) > 1 and self._framewin() is not None:
-            raise ValueError("attention_window_frames cannot be combined with sliding_window_size in the same call yet")
-        if sliding_window is not None and len(sliding_window.windows) > 1:
-            for on, what in ((self.sp_on or plan.world > 1 or branch_exchange is not None, "sequence / CFG-branch parallelism (world > 1)"),
-                             (self.cond_w is not None, "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)"),
-                             (tea_cache is not None, "TeaCache (one residual per window and CFG branch is not implemented)")):
-                if on:
-                    raise ValueError(f"sliding temporal windows cannot be combined with {what} yet")
+        windows = sliding_window is not None and len(sliding_window.windows) > 1
+        parallel = (self.sp_on or plan.world > 1 or branch_exchange is not None) and "sequence / CFG-branch parallelism (world > 1)"
+        options.check_scope(
+            {options.SLIDING: windows and "sliding temporal windows",
+             options.ATTN_WINDOW: windows and self._framewin() is not None and "attention_window_frames",   # alone: _framewin's own check
+             options.SOLVER: solver is not None and f"sample_solver={solver.name!r}",
+             options.CFG_ZERO: guidance is not None and "cfg_zero_star / cfg_zero_init_steps"},
+            {options.SLIDING: windows and "more than one sliding temporal window",
+             (options.ATTN_WINDOW, options.SLIDING): windows and "sliding_window_size in the same call",
+             options.PARALLEL: parallel,
+             (options.CFG_ZERO, options.PARALLEL): parallel and parallel + ": the moments would need an all-reduce",
+             options.I2V: self.cond_w is not None and "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)",
+             options.TEACACHE: tea_cache is not None and "TeaCache (one residual per window and CFG branch is not implemented)"})
+        if guidance is not None and guidance.optimized_scale and not (ctx_uncond is not None and cfg_scale != 1.0):
+            raise ValueError("cfg_zero_star needs classifier-free guidance (an unconditional context and cfg_scale != 1)")
+        if solver is not None and (len(solver.sigmas) != len(scheduler.sigmas) or any(a != b for a, b in zip(solver.sigmas, scheduler.sigmas))):
+            raise ValueError("denoise: the solver plan was not built on this scheduler's sigmas")
+        if windows:
             use_cfg = ctx_uncond is not None and cfg_scale != 1.0
             return self._denoise_windows(latent, [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], buf_tokens, scheduler, cfg_scale,
                                          steps, on_step, round_bf16, sliding_window)

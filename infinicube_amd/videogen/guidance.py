@@ -58,25 +58,3 @@ def validate(cfg_zero_star, cfg_zero_init_steps, num_steps: int, cfg_scale: floa
     if not cfg_zero_star and k == 0:
         return None
     return GuidancePlan(bool(cfg_zero_star), int(k))
-
-
-def env_star(value: Optional[str]) -> Optional[bool]:
-    """ICV_CFG_ZERO_STAR: "0" or "1", or unset."""
-    if value is None or value == "":
-        return None
-    if value.strip() not in ("0", "1"):
-        raise ValueError(f"{ENV_STAR} must be 0 or 1, got {value!r}")
-    return value.strip() == "1"
-
-
-def env_init_steps(value: Optional[str]) -> Optional[int]:
-    """ICV_CFG_ZERO_INIT_STEPS: an integer >= 0, or unset."""
-    if value is None or value == "":
-        return None
-    try:
-        n = int(value)
-    except ValueError:
-        n = -1
-    if n < 0 or str(n) != value.strip():
-        raise ValueError(f"{ENV_INIT_STEPS} must be an integer >= 0, got {value!r}")
-    return n

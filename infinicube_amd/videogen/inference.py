@@ -18,6 +18,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import options
 from .io import load_state_dict, save_video
 from .pipeline import ModelConfig, WanVideoPipeline
 
@@ -30,6 +31,16 @@ DEFAULT_NEGATIVE_PROMPT = (
 # (model id, display name) by size; the three files per model are DiT shards, UMT5 encoder, Wan VAE
 _BASE_MODELS = {True: ("Wan-AI/Wan2.1-T2V-1.3B", "Wan2.1-T2V-1.3B"), False: ("Wan-AI/Wan2.1-T2V-14B", "Wan2.1-T2V-14B")}
 _BASE_FILES = ("diffusion_pytorch_model*.safetensors", "models_t5_umt5-xxl-enc-bf16.pth", "Wan2.1_VAE.pth")
+
+# the features a worker pool (ICV_WORLD > 1) cannot run yet (options.SCOPE): how generate() names each, and why it is single-rank
+_SINGLE_RANK = {
+    options.SLIDING: ("sliding_window_size / sliding_window_stride (ICV_SLIDING_WINDOW_SIZE / _STRIDE)", "the worker pool's ranks shard ONE forward"),
+    options.V2V: ("input_video / denoising_strength (ICV_INPUT_VIDEO / ICV_DENOISING_STRENGTH)", "the start latent is noised in one process"),
+    options.ATTN_WINDOW: ("attention_window_frames / attention_sink_frames (ICV_ATTN_WINDOW_FRAMES / ICV_ATTN_SINK_FRAMES)",
+                          "the frame-windowed launch is single-rank"),
+    options.SOLVER: ("sample_solver (ICV_SAMPLE_SOLVER)", "the multistep update is single-rank"),
+    options.CFG_ZERO: ("cfg_zero_star / cfg_zero_init_steps (ICV_CFG_ZERO_STAR / ICV_CFG_ZERO_INIT_STEPS)", "the scale's moments are single-rank"),
+}
 
 
 def _strip_prefix_group(state_dict: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
@@ -147,21 +158,10 @@ class WanVideoGenerator:
 
         print("Executing video generation...")
         if self._pool is not None:     # the N ranks behind this generator run the request; rank 0's frames come back
-            if getattr(self.pipe, "sliding_window_size", None) is not None or getattr(self.pipe, "sliding_window_stride", None) is not None:
-                raise ValueError("sliding_window_size / sliding_window_stride (ICV_SLIDING_WINDOW_SIZE / _STRIDE) cannot be combined with "
-                                 "ICV_WORLD > 1 (the worker pool's ranks shard ONE forward) yet")
-            if getattr(self.pipe, "input_video", None) is not None or getattr(self.pipe, "denoising_strength", None) is not None:
-                raise ValueError("input_video / denoising_strength (ICV_INPUT_VIDEO / ICV_DENOISING_STRENGTH) cannot be combined with "
-                                 "ICV_WORLD > 1 (the start latent is noised in one process) yet")
-            if getattr(self.pipe, "attention_window_frames", None) is not None or getattr(self.pipe, "attention_sink_frames", None) is not None:
-                raise ValueError("attention_window_frames / attention_sink_frames (ICV_ATTN_WINDOW_FRAMES / ICV_ATTN_SINK_FRAMES) cannot be "
-                                 "combined with ICV_WORLD > 1 (the frame-windowed launch is single-rank) yet")
-            if getattr(self.pipe, "sample_solver", None) not in (None, "euler"):
-                raise ValueError("sample_solver (ICV_SAMPLE_SOLVER) cannot be combined with ICV_WORLD > 1 (the multistep update is "
-                                 "single-rank) yet")
-            if getattr(self.pipe, "cfg_zero_star", None) or getattr(self.pipe, "cfg_zero_init_steps", None):
-                raise ValueError("cfg_zero_star / cfg_zero_init_steps (ICV_CFG_ZERO_STAR / ICV_CFG_ZERO_INIT_STEPS) cannot be combined with "
-                                 "ICV_WORLD > 1 (the scale's moments are single-rank) yet")
+            on = options.switched_on(self.pipe)      # by the client pipeline's attributes: there are no keywords on this route
+            single = [f for f, condition in options.SCOPE if condition == options.PARALLEL]
+            options.check_scope({f: f in on and _SINGLE_RANK[f][0] for f in single},
+                                {(f, options.PARALLEL): f"ICV_WORLD > 1 ({_SINGLE_RANK[f][1]})" for f in single})
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import attn_window, guidance, lora, multigpu, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -260,72 +261,20 @@ class WanVideoPipeline:
         self.buffer_embedder: Optional[BufferEmbedder] = None
         # sampling defaults of the fork's __call__ ([EXT]); the reference never
         # overrides them [R infinicube/videogen/inference.py:216-226], so they are attributes here
-        self.num_inference_steps, self.cfg_scale, self.sigma_shift = 50, 5.0, 5.0
+        self.cfg_scale, self.sigma_shift = 5.0, 5.0
+        # the opt-in settings (options.OPTIONS: TeaCache, sliding windows, LoRA, video-to-video, attention window, solver and step
+        # count, CFG-Zero*), each from its variable for the caller of the unchanged WanVideoGenerator; all off by default, 50 steps
+        for name, value in options.from_env(os.environ).items():
+            setattr(self, name, value)
+        solver.validate(self.sample_solver)
+        for name in options.RECORDS.values():    # what the last call did with each feature; lora_record: what is merged now
+            setattr(self, name, None)
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
         # checkpoint was sampled with during fine-tuning validation).
         self.reference_rounding = os.environ.get("ICV_REFERENCE_ROUNDING", "0") == "1"
         self.scheduler = FlowMatchScheduler(self.num_inference_steps, self.sigma_shift, self.reference_rounding)
-        # TeaCache step skipping (teacache.py; upstream DiffSynth's keywords of the same names).  Off by default; the caller of the
-        # unchanged WanVideoGenerator opts in with ICV_TEACACHE_L1_THRESH (+ ICV_TEACACHE_MODEL_ID; without it a t2v DiT's id is
-        # inferred from its width).  pipe.tea_cache_record: the last call's schedule (None when it ran every step).
-        env_thresh = os.environ.get("ICV_TEACACHE_L1_THRESH")
-        self.tea_cache_l1_thresh: Optional[float] = float(env_thresh) if env_thresh else None
-        self.tea_cache_model_id = os.environ.get("ICV_TEACACHE_MODEL_ID", "")
-        self.tea_cache_record: Optional[dict] = None
-        # Sliding temporal windows for clips longer than one trained forward (sliding_window.py; upstream DiffSynth's keywords of
-        # the same names, in LATENT frames).  Off by default; the caller of the unchanged WanVideoGenerator opts in with
-        # ICV_SLIDING_WINDOW_SIZE + ICV_SLIDING_WINDOW_STRIDE.  pipe.sliding_window_record: the last call's windows
-        # [(frame0, frame1), ...] (None when the call ran one forward per step and branch).
-        from . import sliding_window as _sw
-        self.sliding_window_size: Optional[int] = _sw.env_int(_sw.ENV_SIZE, os.environ.get(_sw.ENV_SIZE))
-        self.sliding_window_stride: Optional[int] = _sw.env_int(_sw.ENV_STRIDE, os.environ.get(_sw.ENV_STRIDE))
-        self.sliding_window_record: Optional[list] = None
-        # LoRA adapters merged into the DiT's projection weights in HBM (lora.py; upstream DiffSynth's pipe.load_lora).  None by
-        # default; the caller of the unchanged WanVideoGenerator names files with ICV_LORA="pathA:0.8,pathB" (alpha defaults to 1),
-        # read here and loaded when the engine is first needed (the DiT they are validated against arrives after construction).
-        # pipe.lora_record: what is currently merged, [{path, alpha, matrices, rank}] (None when nothing is).
-        from . import lora as _lora
-        self.loras: List[dict] = [dict(path=p, alpha=a, adapter=None) for p, a in _lora.parse_env(os.environ.get(_lora.ENV))]
-        self.lora_record: Optional[list] = None
-        # Video-to-video (v2v.py; upstream DiffSynth's keywords of the same names): start from the VAE-encoded input clip noised to
-        # the first sigma of a denoising_strength-shortened range.  Off by default; the caller of the unchanged WanVideoGenerator
-        # opts in with ICV_INPUT_VIDEO (a .npy of uint8 [N, H, W, 3] or a directory of images, read per call) +
-        # ICV_DENOISING_STRENGTH.  pipe.v2v_record: {"denoising_strength", "sigma_0"} of the last call (None when it started from noise).
-        from . import v2v as _v2v
-        self.input_video = os.environ.get(_v2v.ENV_VIDEO) or None
-        self.denoising_strength: Optional[float] = _v2v.env_strength(os.environ.get(_v2v.ENV_STRENGTH))
-        self.v2v_record: Optional[dict] = None
-        # Frame-windowed self-attention (attn_window.py): every query reads the latent frames within
-        # attention_window_frames of its own plus the first attention_sink_frames frames.  Off by default; the caller of the unchanged
-        # WanVideoGenerator opts in with ICV_ATTN_WINDOW_FRAMES (+ ICV_ATTN_SINK_FRAMES).  pipe.attention_window_record:
-        # {"window", "sink", "key_fraction"} of the last call (None when its attention was dense).
-        from . import attn_window as _aw
-        self.attention_window_frames: Optional[int] = _aw.env_int(_aw.ENV_WINDOW, os.environ.get(_aw.ENV_WINDOW))
-        self.attention_sink_frames: Optional[int] = _aw.env_int(_aw.ENV_SINK, os.environ.get(_aw.ENV_SINK))
-        self.attention_window_record: Optional[dict] = None
-        # Multistep sampler (solver.py; Wan2.1's keyword of the same name): "unipc" replaces the Euler update that ends
-        # a step, same two forwards per step.  None / "euler" = today's path.  The caller of the unchanged WanVideoGenerator opts in
-        # with ICV_SAMPLE_SOLVER, and sets the step count of ANY solver with ICV_SAMPLE_STEPS (an integer >= 1; unset = 50).
-        # pipe.solver_record: {"name", "steps", "orders"} of the last call (None when it ran Euler steps).
-        from . import solver as _solver
-        self.sample_solver: Optional[str] = os.environ.get(_solver.ENV_SOLVER) or None
-        _solver.validate(self.sample_solver)
-        env_steps = _solver.env_steps(os.environ.get(_solver.ENV_STEPS))
-        if env_steps is not None:
-            self.num_inference_steps = env_steps
-            self.scheduler = FlowMatchScheduler(self.num_inference_steps, self.sigma_shift, self.reference_rounding)
-        self.solver_record: Optional[dict] = None
-        # CFG-Zero* guidance (guidance.py): cfg_zero_star scales the unconditional velocity of every step by its
-        # projection coefficient onto the conditional one before the CFG combine; cfg_zero_init_steps = K runs nothing in the first K
-        # steps.  Off by default; the caller of the unchanged WanVideoGenerator opts in with ICV_CFG_ZERO_STAR (0 / 1) and
-        # ICV_CFG_ZERO_INIT_STEPS (an integer >= 0).  pipe.guidance_record: {"optimized_scale", "zero_init_steps", "scales"} of the
-        # last call (None when both were off).
-        from . import guidance as _guidance
-        self.cfg_zero_star: Optional[bool] = _guidance.env_star(os.environ.get(_guidance.ENV_STAR))
-        self.cfg_zero_init_steps: Optional[int] = _guidance.env_init_steps(os.environ.get(_guidance.ENV_INIT_STEPS))
-        self.guidance_record: Optional[dict] = None
         self._ops = ops
         self._engine = None
         self._engine_key = None
@@ -379,7 +328,6 @@ class WanVideoPipeline:
         """Upstream's ``pipe.load_lora(pipe.dit, path, alpha=1)``: ``W += alpha * lora_B @ lora_A`` on the DiT's attention and FFN
         linears.  Parses and validates the file against the DiT's shape now (host only); the merge into HBM happens when the
         engine is next needed, adapters in the order they were loaded, one bf16 rounding each (dit.WanDiT.apply_lora)."""
-        from . import lora
         if getattr(self, "remote", False):
             raise RuntimeError(f"load_lora: this pipeline is the client of a multi-GPU worker pool and holds no weights; name the "
                                f"adapter in {lora.ENV}=\"path:alpha,...\" before the generator is built (every rank merges into its own replica)")
@@ -396,7 +344,6 @@ class WanVideoPipeline:
     def _reconcile_lora(self, engine):
         """Make the engine's merged adapters equal ``self.loras``: merge what is missing when the merged ones are a prefix of the
         wanted list, else restore the touched matrices and merge all.  Nothing wanted and nothing merged: no work at all."""
-        from . import lora
         for e in self.loras:
             if e["adapter"] is None:              # an ICV_LORA entry: loaded on first use
                 e["adapter"] = lora.load_adapter(e["path"])
@@ -496,36 +443,6 @@ class WanVideoPipeline:
         msk = msk.reshape(grid.T, 4, h // 8, w // 8).transpose(0, 1)                    # [4, T, h8, w8]
         return torch.cat([msk, lat], dim=0)
 
-    def _tea_cache_settings(self, thresh: Optional[float], model_id: str, cfg: WanDiTConfig):
-        """(threshold, model id) in effect for one call: the keyword, else the attribute (set from the environment at construction).
-        A threshold without an id raises DiffSynth's unknown-id error, except when both came from the environment: then a t2v
-        DiT's id follows from its width.  (None, "") = TeaCache off."""
-        from . import teacache
-        from_env = thresh is None and not model_id and "ICV_TEACACHE_L1_THRESH" in os.environ and not self.tea_cache_model_id
-        thresh = self.tea_cache_l1_thresh if thresh is None else thresh
-        model_id = model_id or self.tea_cache_model_id
-        if thresh is None:
-            return None, ""
-        if not model_id and from_env:
-            model_id = teacache.infer_t2v_model_id(cfg)
-        teacache.coefficients(model_id)          # validate before any work is done
-        return float(thresh), model_id
-
-    def _sliding_window_settings(self, size: Optional[int], stride: Optional[int]):
-        """(size, stride) in latent frames in effect for one call - each from the keyword, else the attribute (set from the
-        environment at construction) - validated; None = off."""
-        from . import sliding_window
-        return sliding_window.validate(self.sliding_window_size if size is None else size,
-                                       self.sliding_window_stride if stride is None else stride)
-
-    def _attention_window_settings(self, window: Optional[int], sink: Optional[int], T: int):
-        """(window, sink) in latent frames in effect for one call of T latent frames - each from the keyword, else the attribute (set
-        from the environment at construction) - validated; None = dense attention (off, or a window that covers the clip)."""
-        from . import attn_window
-        aw = attn_window.validate(self.attention_window_frames if window is None else window,
-                                  self.attention_sink_frames if sink is None else sink, T)
-        return None if aw is None or attn_window.dense(T, aw[0]) else aw
-
     # ---- D5: the generation call -----------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: str, negative_prompt: str = "", semantic_buffer_video=None,
@@ -541,74 +458,55 @@ class WanVideoPipeline:
                  cfg_zero_init_steps: Optional[int] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
-        num_inference_steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
+        opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
+        num_inference_steps = opt.num_inference_steps
         cfg_scale = self.cfg_scale if cfg_scale is None else cfg_scale
         sigma_shift = self.sigma_shift if sigma_shift is None else sigma_shift
         grid = TokenGrid(num_frames, height, width)
-        # sliding temporal windows: settings and scope are checked before any GPU work (the engine packs the weights into HBM)
-        sw_plan = None
-        sw = self._sliding_window_settings(sliding_window_size, sliding_window_stride)
-        if sw is not None:
-            from . import sliding_window
-            sw_plan = sliding_window.plan(grid.T, *sw)
-            if len(sw_plan.windows) == 1:        # the clip fits one window: today's path, same launches, same bits
-                sw_plan = None
-        self.sliding_window_record = sw_plan.record() if sw_plan is not None else None
-        # frame-windowed self-attention: validated here too; a window that covers the clip is today's path, same launches, same bits
-        aw = self._attention_window_settings(attention_window_frames, attention_sink_frames, grid.T)
-        if aw is not None and sw_plan is not None:         # more than one window, as the engine's own check (WanDiT.denoise) has it
-            raise ValueError("attention_window_frames / attention_sink_frames cannot be combined with sliding_window_size in the same call yet")
-        if aw is not None and self.attn_dtype == "fp8":
-            raise ValueError("attention_window_frames / attention_sink_frames cannot be combined with the e4m3 self-attention mode "
-                             "(torch_dtype=float8_e4m3fn) yet")
-        self.attention_window_record = None
-        # multistep sampler: the name is validated here, its scope below, both before any GPU work
-        from . import solver as _solver
-        solver_name = _solver.validate(self.sample_solver if sample_solver is None else sample_solver)
-        self.solver_record = None
-        if solver_name is not None and sw_plan is not None:
-            raise ValueError(f"sample_solver={solver_name!r} cannot be combined with sliding_window_size (more than one window) in the same call yet")
-        # CFG-Zero* guidance: values here, scope below, both before any GPU work
-        from . import guidance as _guidance
-        gd_plan = _guidance.validate(self.cfg_zero_star if cfg_zero_star is None else cfg_zero_star,
-                                     self.cfg_zero_init_steps if cfg_zero_init_steps is None else cfg_zero_init_steps,
-                                     num_inference_steps, cfg_scale)
-        self.guidance_record = None
-        if gd_plan is not None and sw_plan is not None:
-            raise ValueError("cfg_zero_star / cfg_zero_init_steps cannot be combined with sliding_window_size (more than one window) in the same call yet")
+        for feature, name in options.RECORDS.items():
+            if feature != options.LORA:              # what is merged outlives a call: _reconcile_lora owns that record
+                setattr(self, name, None)
+        # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
+        # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
+        # same bits), the attention window when it does not cover the clip (the same).
+        sw = sliding_window.validate(opt.sliding_window_size, opt.sliding_window_stride)
+        sw_plan = sliding_window.plan(grid.T, *sw) if sw is not None else None
+        if sw_plan is not None and len(sw_plan.windows) > 1:
+            self.sliding_window_record = sw_plan.record()
+        else:
+            sw_plan = None
+        aw = attn_window.validate(opt.attention_window_frames, opt.attention_sink_frames, grid.T)
+        if aw is not None and attn_window.dense(grid.T, aw[0]):
+            aw = None
+        solver_name = solver.validate(opt.sample_solver)
+        gd_plan = guidance.validate(opt.cfg_zero_star, opt.cfg_zero_init_steps, num_inference_steps, cfg_scale)
         first_step = gd_plan.zero_init_steps if gd_plan is not None else 0        # the first step that runs: where solver and TeaCache begin
-        # video-to-video: the clip is read (a path) and both settings are checked here, before any GPU work
-        from . import v2v
-        v2v_frames, strength = v2v.validate(self.input_video if input_video is None else input_video,
-                                            self.denoising_strength if denoising_strength is None else denoising_strength, num_frames)
-        self.v2v_record = None
+        v2v_frames, strength = v2v.validate(opt.input_video, opt.denoising_strength, num_frames)      # reads the clip (a path)
         world, rank = 1, 0
-        from . import multigpu
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and not multigpu.degraded():   # degraded: a failed multi-GPU start
                 world, rank = dist.get_world_size(), dist.get_rank()                        # left a dead group behind
         except Exception:  # pragma: no cover
             pass
-        if sw_plan is not None:
-            # first-version scope: each of these raises, none falls back to one full-length forward
-            tc_on = (self.tea_cache_l1_thresh if tea_cache_l1_thresh is None else tea_cache_l1_thresh) is not None
-            for on, what in ((world > 1, f"a process group of {world} ranks"),
-                             (self.dit.cfg.has_image_input, "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)"),
-                             (tc_on, "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call")):
-                if on:
-                    raise ValueError(f"sliding_window_size / sliding_window_stride cannot be combined with {what} yet")
-        if aw is not None and world > 1:
-            raise ValueError(f"attention_window_frames / attention_sink_frames cannot be combined with a process group of {world} ranks yet")
-        if solver_name is not None and world > 1:
-            raise ValueError(f"sample_solver={solver_name!r} cannot be combined with a process group of {world} ranks yet")
-        if gd_plan is not None and world > 1:
-            raise ValueError(f"cfg_zero_star / cfg_zero_init_steps cannot be combined with a process group of {world} ranks yet")
-        if v2v_frames is not None and world > 1:
-            raise ValueError(f"input_video / denoising_strength cannot be combined with a process group of {world} ranks yet")
+        # first-version scope: each of these raises, none falls back (to one full-length forward, to dense attention, to Euler ...)
+        windows = sw_plan is not None
+        options.check_scope(
+            {options.SLIDING: windows and "sliding_window_size / sliding_window_stride",
+             options.ATTN_WINDOW: aw is not None and "attention_window_frames / attention_sink_frames",
+             options.SOLVER: solver_name is not None and f"sample_solver={solver_name!r}",
+             options.CFG_ZERO: gd_plan is not None and "cfg_zero_star / cfg_zero_init_steps",
+             options.V2V: v2v_frames is not None and "input_video / denoising_strength"},
+            {options.SLIDING: windows and "sliding_window_size (more than one window) in the same call",
+             (options.ATTN_WINDOW, options.SLIDING): windows and "sliding_window_size in the same call",
+             options.PARALLEL: world > 1 and f"a process group of {world} ranks",
+             options.I2V: self.dit.cfg.has_image_input and "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)",
+             options.TEACACHE: opt.tea_cache_l1_thresh is not None and "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call",
+             options.FP8_ATTN: self.attn_dtype == "fp8" and "the e4m3 self-attention mode (torch_dtype=float8_e4m3fn)"})
         engine = self._get_engine()
         ops = engine.ops
-        tc_thresh, tc_id = self._tea_cache_settings(tea_cache_l1_thresh, tea_cache_model_id, engine.cfg)
+        tc_thresh, tc_id = teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, engine.cfg,
+                                             from_keyword=tea_cache_l1_thresh is not None)
         lkey = (world, rank, self.parallelism, cfg_scale != 1.0)
         # process groups are created once per (world, mode).  Behind a worker pool the cache belongs to the POOL, not to this
         # pipeline object: a second generator on the same pool gives rank 0 a new pipeline while the workers keep theirs, and
@@ -636,7 +534,6 @@ class WanVideoPipeline:
         if aw is not None or engine.attn_window is not None:
             engine.set_attention_window(*(aw or (None, None)))
         if aw is not None:
-            from . import attn_window
             self.attention_window_record = attn_window.record(grid.T, *aw)
         self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding, denoising_strength=strength)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
@@ -716,7 +613,6 @@ class WanVideoPipeline:
         # per-layer K|V exchange of a computed step would wait for a rank that skipped it)
         tc_plan = None
         if tc_thresh is not None:
-            from . import teacache
             if rank == 0:
                 tc_plan = teacache.plan(engine, self.scheduler, tc_thresh, tc_id, range(first_step, num_inference_steps))
             if world > 1:
@@ -726,7 +622,7 @@ class WanVideoPipeline:
         self.tea_cache_record = tc_plan.record() if tc_plan is not None else None
         solver_plan = None
         if solver_name is not None:
-            solver_plan = _solver.MultistepPlan(solver_name, self.scheduler.sigmas)
+            solver_plan = solver.MultistepPlan(solver_name, self.scheduler.sigmas)
             self.solver_record = solver_plan.record(range(first_step, num_inference_steps))
         # the hot loop (HIP)
         it = range(num_inference_steps)
@@ -734,9 +630,7 @@ class WanVideoPipeline:
             it = progress_bar_cmd(it)
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
-                       round_bf16=self.reference_rounding, tea_cache=tc_plan, **(dict(sliding_window=sw_plan) if sw_plan is not None else {}),
-                       **(dict(solver=solver_plan) if solver_plan is not None else {}),
-                       **(dict(guidance=gd_plan) if gd_plan is not None else {}))
+                       round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan)
         if gd_plan is not None:
             self.guidance_record = gd_plan.record(engine.guidance_scales)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)

@@ -45,16 +45,6 @@ def validate(size, stride) -> Optional[Tuple[int, int]]:
     return size, stride
 
 
-def env_int(name: str, value: Optional[str]) -> Optional[int]:
-    """The value of an ICV_SLIDING_WINDOW_* variable -> int (unset / "" -> None); anything but an integer raises ValueError."""
-    if value is None or value == "":
-        return None
-    try:
-        return int(value)
-    except ValueError:
-        raise ValueError(f"{name} must be an integer number of latent frames, got {value!r}") from None
-
-
 def windows(T: int, size: int, stride: int) -> Tuple[Tuple[int, int], ...]:
     out = []
     for t in range(0, T, stride):

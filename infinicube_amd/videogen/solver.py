@@ -34,19 +34,6 @@ def validate(name) -> Optional[str]:
     return name
 
 
-def env_steps(value: Optional[str]) -> Optional[int]:
-    """ICV_SAMPLE_STEPS: an integer >= 1, or unset."""
-    if value is None or value == "":
-        return None
-    try:
-        n = int(value)
-    except ValueError:
-        n = 0
-    if n < 1 or str(n) != value.strip():
-        raise ValueError(f"{ENV_STEPS} must be an integer >= 1, got {value!r}")
-    return n
-
-
 def lam(sigma: float) -> float:
     """Half log-SNR of the flow-match path: ln((1 - sigma) / sigma)."""
     if sigma <= 0.0:

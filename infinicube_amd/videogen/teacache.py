@@ -15,11 +15,14 @@ float64.  The same schedule holds for both CFG branches and for every sequence-p
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+ENV_THRESH, ENV_MODEL_ID = "ICV_TEACACHE_L1_THRESH", "ICV_TEACACHE_MODEL_ID"
 
 # Polynomial coefficients, highest degree first (np.poly1d), as published with TeaCache4Wan2.1 and copied into DiffSynth.
 # Not checked against a copy of upstream (ORACLE_RISKS.md R16); tests/test_teacache_cpu.py pins them.
@@ -50,6 +53,18 @@ def infer_t2v_model_id(cfg) -> str:
     if cfg.dim not in T2V_MODEL_ID_BY_DIM:
         raise ValueError(f"TeaCache: no t2v model id for a DiT of width {cfg.dim}; pass tea_cache_model_id / ICV_TEACACHE_MODEL_ID")
     return T2V_MODEL_ID_BY_DIM[cfg.dim]
+
+
+def settings(thresh: Optional[float], model_id: str, cfg, from_keyword: bool):
+    """(threshold, model id) of one call, validated, from the values in effect (options.resolve); (None, "") = TeaCache off.
+    A threshold without an id raises DiffSynth's unknown-id error, except when neither was a keyword and the threshold's variable
+    is set: then a t2v DiT's id follows from its width."""
+    if thresh is None:
+        return None, ""
+    if not model_id and not from_keyword and ENV_THRESH in os.environ:
+        model_id = infer_t2v_model_id(cfg)
+    coefficients(model_id)          # validate before any work is done
+    return float(thresh), model_id
 
 
 @dataclass

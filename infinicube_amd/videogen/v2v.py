@@ -23,16 +23,6 @@ ENV_VIDEO, ENV_STRENGTH = "ICV_INPUT_VIDEO", "ICV_DENOISING_STRENGTH"
 FORMS = "a .npy file of uint8 [N, H, W, 3] frames, or a directory of image files (read in sorted order)"
 
 
-def env_strength(value: Optional[str]) -> Optional[float]:
-    """The value of ICV_DENOISING_STRENGTH -> float (unset / "" -> None); anything but a number raises ValueError."""
-    if value is None or value == "":
-        return None
-    try:
-        return float(value)
-    except ValueError:
-        raise ValueError(f"{ENV_STRENGTH} must be a number in (0, 1], got {value!r}") from None
-
-
 def _frames_of_array(a: np.ndarray, what: str) -> List[Image.Image]:
     if a.ndim != 4 or a.shape[-1] != 3 or a.dtype != np.uint8:
         raise ValueError(f"{what}: expected uint8 frames [N, H, W, 3], got {a.dtype} {tuple(a.shape)}")

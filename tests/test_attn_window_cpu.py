@@ -9,6 +9,7 @@ import torch
 
 from dit_launch_trace import Trace, TracedOps
 from infinicube_amd.videogen import attn_window as AW
+from infinicube_amd.videogen import options
 from infinicube_amd.videogen import synthetic as syn
 from infinicube_amd.videogen.config import TokenGrid, preset
 from infinicube_amd.videogen.dit import WanDiT
@@ -18,8 +19,7 @@ from oracle import wan_ref as R
 from oracle_ops import OracleOps
 
 CFG, GRID = preset("tiny"), TokenGrid(17, 64, 96)        # 5 latent frames of 4 x 6 tokens
-ENV = ("ICV_ATTN_WINDOW_FRAMES", "ICV_ATTN_SINK_FRAMES", "ICV_SLIDING_WINDOW_SIZE", "ICV_SLIDING_WINDOW_STRIDE",
-       "ICV_TEACACHE_L1_THRESH", "ICV_TEACACHE_MODEL_ID", "ICV_WORLD")
+ENV = options.ENV_NAMES
 BF16 = torch.bfloat16
 
 
@@ -169,23 +169,30 @@ def test_settings_are_checked_before_any_gpu_work(monkeypatch):
         p(**_call_kw(attention_window_frames=1, sliding_window_size=4, sliding_window_stride=2))
 
 
+def _settings(p, window, sink, T):
+    """What WanVideoPipeline.__call__ does with its two keywords: keyword or attribute, the feature's validation, dense = off."""
+    opt = options.resolve(p, dict(attention_window_frames=window, attention_sink_frames=sink))
+    aw = AW.validate(opt.attention_window_frames, opt.attention_sink_frames, T)
+    return None if aw is None or AW.dense(T, aw[0]) else aw
+
+
 def test_settings_precedence_and_record(monkeypatch):
     for k in ENV:
         monkeypatch.delenv(k, raising=False)
     T = GRID.T
     p = _pipe()
     assert (p.attention_window_frames, p.attention_sink_frames, p.attention_window_record) == (None, None, None)
-    assert p._attention_window_settings(None, None, T) is None                         # off by default
-    assert p._attention_window_settings(1, 1, T) == (1, 1)
+    assert _settings(p, None, None, T) is None                         # off by default
+    assert _settings(p, 1, 1, T) == (1, 1)
     monkeypatch.setenv("ICV_ATTN_WINDOW_FRAMES", "2")
     monkeypatch.setenv("ICV_ATTN_SINK_FRAMES", "1")
     p = _pipe()
     assert (p.attention_window_frames, p.attention_sink_frames) == (2, 1)             # environment -> attributes
-    assert p._attention_window_settings(None, None, T) == (2, 1)
-    assert p._attention_window_settings(1, 0, T) == (1, 0)                             # keywords win
-    assert p._attention_window_settings(1, None, T) == (1, 1)                          # ... each on its own
+    assert _settings(p, None, None, T) == (2, 1)
+    assert _settings(p, 1, 0, T) == (1, 0)                             # keywords win
+    assert _settings(p, 1, None, T) == (1, 1)                          # ... each on its own
     p.attention_window_frames, p.attention_sink_frames = 0, 2                          # attributes set after construction
-    assert p._attention_window_settings(None, None, T) == (0, 2)
+    assert _settings(p, None, None, T) == (0, 2)
     monkeypatch.delenv("ICV_ATTN_WINDOW_FRAMES")
     with pytest.raises(ValueError, match="needs attention_window_frames"):            # the anchor variable alone
         _pipe()(**_call_kw())

@@ -33,11 +33,9 @@ from infinicube_amd.videogen.scheduler import FlowMatchScheduler, flow_match_sig
 from infinicube_amd.videogen.seqpar import ShardPlan
 from oracle import wan_ref as R
 from standins import HashTextEncoder, PoolVAE
-from test_solver_cpu import CFG, GRID, LOOP_STEPS, CountingVAE, SolverOps, generator_through_env, rb, restated_sample
-from test_solver_cpu import ENV as SOLVER_ENV
+from test_solver_cpu import CFG, ENV, GRID, LOOP_STEPS, CountingVAE, SolverOps, generator_through_env, rb, restated_sample
 from test_solver_cpu import inputs as solver_inputs
 
-ENV = SOLVER_ENV + (G.ENV_STAR, G.ENV_INIT_STEPS)
 F32, F64 = torch.float32, torch.float64
 WORKSPACE = 512                      # ICV_CFG_ZERO_WORKSPACE_DOUBLES
 CFG_SCALE = 5.0

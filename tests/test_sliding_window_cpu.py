@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from dit_launch_trace import Trace, TracedOps
+from infinicube_amd.videogen import options
 from infinicube_amd.videogen import sliding_window as SW
 from infinicube_amd.videogen import synthetic as syn
 from infinicube_amd.videogen.config import TokenGrid, preset
@@ -18,7 +19,7 @@ from oracle_ops import OracleOps
 
 CFG, GRID = preset("tiny"), TokenGrid(33, 64, 96)        # 9 latent frames of 4 x 6 tokens
 CASES = [(9, 4, 2), (48, 24, 12), (48, 24, 18), (30, 24, 12), (47, 24, 12), (27, 8, 8), (9, 4, 1), (20, 24, 12)]
-ENV = ("ICV_SLIDING_WINDOW_SIZE", "ICV_SLIDING_WINDOW_STRIDE", "ICV_TEACACHE_L1_THRESH", "ICV_TEACACHE_MODEL_ID", "ICV_WORLD")
+ENV = options.ENV_NAMES
 
 
 def window_euler_twin(latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
@@ -200,22 +201,28 @@ def test_worker_pool_combination_raises(monkeypatch):
         g.generate(sem, co, seed=0)
 
 
+def _settings(p, size, stride):
+    """What WanVideoPipeline.__call__ does with its two keywords: keyword or attribute, then the feature's validation."""
+    opt = options.resolve(p, dict(sliding_window_size=size, sliding_window_stride=stride))
+    return SW.validate(opt.sliding_window_size, opt.sliding_window_stride)
+
+
 def test_settings_precedence_and_record(monkeypatch):
     for k in ENV:
         monkeypatch.delenv(k, raising=False)
     p = _pipe()
     assert (p.sliding_window_size, p.sliding_window_stride, p.sliding_window_record) == (None, None, None)
-    assert p._sliding_window_settings(None, None) is None                          # off by default
-    assert p._sliding_window_settings(4, 2) == (4, 2)
+    assert _settings(p, None, None) is None                          # off by default
+    assert _settings(p, 4, 2) == (4, 2)
     monkeypatch.setenv("ICV_SLIDING_WINDOW_SIZE", "6")
     monkeypatch.setenv("ICV_SLIDING_WINDOW_STRIDE", "3")
     p = _pipe()
     assert (p.sliding_window_size, p.sliding_window_stride) == (6, 3)              # environment -> attributes
-    assert p._sliding_window_settings(None, None) == (6, 3)
-    assert p._sliding_window_settings(4, 2) == (4, 2)                              # keywords win
-    assert p._sliding_window_settings(4, None) == (4, 3)                           # ... each on its own
+    assert _settings(p, None, None) == (6, 3)
+    assert _settings(p, 4, 2) == (4, 2)                              # keywords win
+    assert _settings(p, 4, None) == (4, 3)                           # ... each on its own
     p.sliding_window_size, p.sliding_window_stride = 5, 5                          # attributes set after construction
-    assert p._sliding_window_settings(None, None) == (5, 5)
+    assert _settings(p, None, None) == (5, 5)
     monkeypatch.delenv("ICV_SLIDING_WINDOW_STRIDE")
     with pytest.raises(ValueError, match="together"):                              # only one of the two variables
         _pipe()(**_call_kw())

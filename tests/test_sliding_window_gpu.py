@@ -17,12 +17,11 @@ from infinicube_amd.videogen.config import TokenGrid, preset
 from infinicube_amd.videogen.dit import WanDiT
 from infinicube_amd.videogen.scheduler import FlowMatchScheduler
 from oracle import wan_ref as R
-from test_sliding_window_cpu import (CFG, GRID, _inputs, _window_loop, manual_window_loop, sliding_window_reference,
+from test_sliding_window_cpu import (CFG, ENV, GRID, _inputs, _window_loop, manual_window_loop, sliding_window_reference,
                                      window_euler_twin)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ENV = ("ICV_SLIDING_WINDOW_SIZE", "ICV_SLIDING_WINDOW_STRIDE", "ICV_TEACACHE_L1_THRESH", "ICV_TEACACHE_MODEL_ID", "ICV_WORLD")
 
 
 # ---- 6. the kernel against its twin ----------------------------------------------------------------------------------------------

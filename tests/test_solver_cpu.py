@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from dit_launch_trace import Trace, TracedOps
+from infinicube_amd.videogen import options
 from infinicube_amd.videogen import solver as S
 from infinicube_amd.videogen import synthetic as syn
 from infinicube_amd.videogen.config import TokenGrid, preset
@@ -23,8 +24,7 @@ from standins import HashTextEncoder, PoolVAE
 from test_teacache_cpu import TeaOps
 
 CFG, GRID = preset("tiny"), TokenGrid(17, 64, 96)        # 5 latent frames of 4 x 6 tokens
-ENV = ("ICV_SAMPLE_SOLVER", "ICV_SAMPLE_STEPS", "ICV_SLIDING_WINDOW_SIZE", "ICV_SLIDING_WINDOW_STRIDE", "ICV_TEACACHE_L1_THRESH",
-       "ICV_TEACACHE_MODEL_ID", "ICV_WORLD", "ICV_INPUT_VIDEO", "ICV_DENOISING_STRENGTH", "ICV_ATTN_WINDOW_FRAMES", "ICV_ATTN_SINK_FRAMES")
+ENV = options.ENV_NAMES
 F32 = torch.float32
 # The step count of the loop tests, chosen in 4..8 on the CPU: on the stiff DiT below the host loop scores 60.6 dB against the restated
 # UniPC loop and the restated Euler loop 37.1 dB - under the 40 dB bar itself (5 steps: 60.8 / 39.2 dB with the head scaled by 6)

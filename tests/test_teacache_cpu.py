@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from infinicube_amd.videogen import multigpu, teacache
+from infinicube_amd.videogen import multigpu, options, teacache
 from infinicube_amd.videogen import synthetic as syn
 from infinicube_amd.videogen.config import TokenGrid, preset
 from infinicube_amd.videogen.dit import WanDiT
@@ -137,32 +137,38 @@ def _pipe(ops=None):
                             ops=ops or TeaOps())
 
 
+def _settings(p, thresh, model_id, cfg):
+    """What WanVideoPipeline.__call__ does with its two keywords: keyword or attribute, then the feature's own rule."""
+    opt = options.resolve(p, dict(tea_cache_l1_thresh=thresh, tea_cache_model_id=model_id or None))
+    return teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, cfg, from_keyword=thresh is not None)
+
+
 def test_settings_precedence(monkeypatch):
-    for k in ("ICV_TEACACHE_L1_THRESH", "ICV_TEACACHE_MODEL_ID"):
+    for k in options.ENV_NAMES:
         monkeypatch.delenv(k, raising=False)
     p = _pipe()
     assert (p.tea_cache_l1_thresh, p.tea_cache_model_id, p.tea_cache_record) == (None, "", None)
-    assert p._tea_cache_settings(None, "", CFG) == (None, "")                                   # off by default
-    assert p._tea_cache_settings(0.2, "Wan2.1-T2V-14B", CFG) == (0.2, "Wan2.1-T2V-14B")
+    assert _settings(p, None, "", CFG) == (None, "")                                   # off by default
+    assert _settings(p, 0.2, "Wan2.1-T2V-14B", CFG) == (0.2, "Wan2.1-T2V-14B")
     with pytest.raises(ValueError, match=" is not a supported TeaCache model id"):             # a threshold with the default id
-        p._tea_cache_settings(0.2, "", CFG)
+        _settings(p, 0.2, "", CFG)
     monkeypatch.setenv("ICV_TEACACHE_L1_THRESH", "0.3")
     monkeypatch.setenv("ICV_TEACACHE_MODEL_ID", "Wan2.1-I2V-14B-480P")
     p = _pipe()
     assert (p.tea_cache_l1_thresh, p.tea_cache_model_id) == (0.3, "Wan2.1-I2V-14B-480P")        # environment -> attributes
-    assert p._tea_cache_settings(None, "", CFG) == (0.3, "Wan2.1-I2V-14B-480P")
-    assert p._tea_cache_settings(0.1, "Wan2.1-T2V-14B", CFG) == (0.1, "Wan2.1-T2V-14B")         # keywords win
+    assert _settings(p, None, "", CFG) == (0.3, "Wan2.1-I2V-14B-480P")
+    assert _settings(p, 0.1, "Wan2.1-T2V-14B", CFG) == (0.1, "Wan2.1-T2V-14B")         # keywords win
     p.tea_cache_l1_thresh, p.tea_cache_model_id = 0.05, "Wan2.1-T2V-1.3B"                       # attributes set after construction
-    assert p._tea_cache_settings(None, "", CFG) == (0.05, "Wan2.1-T2V-1.3B")
+    assert _settings(p, None, "", CFG) == (0.05, "Wan2.1-T2V-1.3B")
     # a threshold from the environment without an id: a t2v DiT's id follows from its width; i2v needs one
     monkeypatch.delenv("ICV_TEACACHE_MODEL_ID")
     p = _pipe()
-    assert p._tea_cache_settings(None, "", dataclasses.replace(CFG, dim=1536)) == (0.3, "Wan2.1-T2V-1.3B")
-    assert p._tea_cache_settings(None, "", dataclasses.replace(CFG, dim=5120)) == (0.3, "Wan2.1-T2V-14B")
+    assert _settings(p, None, "", dataclasses.replace(CFG, dim=1536)) == (0.3, "Wan2.1-T2V-1.3B")
+    assert _settings(p, None, "", dataclasses.replace(CFG, dim=5120)) == (0.3, "Wan2.1-T2V-14B")
     with pytest.raises(ValueError, match="explicit model id"):
-        p._tea_cache_settings(None, "", preset("tiny-i2v"))
+        _settings(p, None, "", preset("tiny-i2v"))
     with pytest.raises(ValueError, match="is not a supported TeaCache model id"):             # a keyword threshold never infers
-        p._tea_cache_settings(0.3, "", dataclasses.replace(CFG, dim=1536))
+        _settings(p, 0.3, "", dataclasses.replace(CFG, dim=1536))
     # the worker ranks behind ICV_WORLD=N get both attributes with every request
     assert {"tea_cache_l1_thresh", "tea_cache_model_id"} <= set(multigpu._PIPE_SETTINGS)
 

@@ -15,7 +15,7 @@ from PIL import Image
 
 from infinicube_amd.videogen import sliding_window as SW
 from infinicube_amd.videogen import synthetic as syn
-from infinicube_amd.videogen import teacache, v2v
+from infinicube_amd.videogen import options, teacache, v2v
 from infinicube_amd.videogen.config import TokenGrid, preset
 from infinicube_amd.videogen.dit import WanDiT
 from infinicube_amd.videogen.pipeline import DiTHolder, WanVideoPipeline, _video_to_tensor, _video_to_uint8
@@ -28,8 +28,7 @@ from test_teacache_cpu import LINEAR, TeaOps
 
 CFG, GRID = preset("tiny"), TokenGrid(33, 64, 96)        # the sliding-window tests' preset: 9 latent frames of 4 x 6 tokens
 SHORT = TokenGrid(9, 64, 96)                             # 3 latent frames: everything that needs no second window
-ENV = ("ICV_INPUT_VIDEO", "ICV_DENOISING_STRENGTH", "ICV_SLIDING_WINDOW_SIZE", "ICV_SLIDING_WINDOW_STRIDE", "ICV_TEACACHE_L1_THRESH",
-       "ICV_TEACACHE_MODEL_ID", "ICV_WORLD", "ICV_REFERENCE_ROUNDING")
+ENV = options.ENV_NAMES + ("ICV_REFERENCE_ROUNDING",)
 TILES = dict(tile_size=(30, 52), tile_stride=(15, 26))   # the pipeline's defaults
 
 
