@@ -9,43 +9,10 @@ import copy
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from infinicube_amd.videogen import vae as V
 from infinicube_amd.videogen import vae_hip as VH
-
-
-class HostVaeHip(VH.VaeHip):
-    """VaeHip with the two kernels restated in torch (the C ABI's contract, fp32 accumulate, one rounding)."""
-
-    def __init__(self, net, device="cpu"):
-        self.net, self.device, self.lib = net, torch.device(device), None
-        self._w, self._g = {}, {}
-
-    def conv(self, x, mod, taps, resid=None, first_frame=0):
-        rec = self._conv_w(mod, taps)
-        assert x.C == rec.cin
-        out = VH.Vol(x.T, x.H, x.W, rec.cout, self.device)
-        m0, m1 = (VH.PT + first_frame) * x.frame_rows, x.rows
-        offs = list(rec.offsets(x.Hp, x.Wp))
-        assert m0 + min(offs) >= -x.margin and (m1 - 1) + max(offs) < m1 + x.margin, "a tap leaves the buffer"
-        W = rec.w.float()[:, : len(taps) * rec.cin].view(rec.cout, len(taps), rec.cin)
-        assert float(rec.w.float()[:, len(taps) * rec.cin:].abs().sum()) == 0.0
-        acc = rec.bias[None].repeat(m1 - m0, 1)
-        for i, off in enumerate(offs):
-            acc = acc + x.buf[x.margin + m0 + off: x.margin + m1 + off].float() @ W[:, i].T
-        if resid is not None:
-            acc = acc + resid.mat[m0:m1].float()
-        out.mat[m0:m1] = acc.to(torch.bfloat16)
-        return out
-
-    def norm_act(self, x, norm, act):
-        out = VH.Vol(x.T, x.H, x.W, x.C, self.device, zero_pads=False)
-        out.buf.zero_()
-        xi = x.interior().float()
-        y = xi / xi.norm(dim=-1, keepdim=True).clamp_min(1e-12) * norm.scale * self._gamma(norm)
-        out.interior().copy_((F.silu(y) if act else y).to(torch.bfloat16))
-        return out
+from vae_trace import HostVaeHip
 
 
 @pytest.fixture(scope="module")
