@@ -39,7 +39,8 @@ extern "C" {
  *    icv_unpatchify_cfg_euler_window (sliding temporal windows); icv_lora_merge_bf16 (LoRA merge in HBM); icv_add_noise_f32
  *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch);
  *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms);
- *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output). */
+ *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output);
+ *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -596,6 +597,27 @@ int icv_lora_merge_bf16(void* W, int64_t ldw, const void* up, int64_t ldu, const
  * pointers: 16-byte vectors where the three pointers share their offset from a 16-byte boundary, element by element before and
  * after that body and everywhere when the offsets differ.  n == 0 launches nothing; negative n or a null pointer is an error. */
 int icv_add_noise_f32(const float* x0, const float* noise, float* out, int64_t n, float sigma, int round_bf16, void* stream);
+
+/* ---- regenerating part of a clip: input_mask ---------------------------------------------------------------
+ * icv_latent_keep_mask_u8: mask u8 [N, H, W] (non-zero = regenerate) -> keep u8 [T, H/8, W/8], T = (N - 1) / 4 + 1.
+ * keep[t, h, w] = 1 iff every mask byte of the cell's stride footprint is 0 - frames {0} for t == 0 and {4t-3 .. 4t} otherwise,
+ * rows 8h .. 8h+7, columns 8w .. 8w+7 - else 0: a cell that touches anything to regenerate is regenerated.  N = 4k + 1 and H, W
+ * multiples of 16 (an error otherwise); H == 0 or W == 0 launches nothing; any mask / keep pointers (8-byte loads where the mask
+ * is 8-byte aligned, bytes otherwise).  Only keep's T * H/8 * W/8 bytes are written. */
+int icv_latent_keep_mask_u8(const uint8_t* mask, uint8_t* keep, int64_t N, int64_t H, int64_t W, void* stream);
+
+/* icv_pin_known_f32: latent, x0, noise (and x_hat, m_new where non-NULL) f32 [C, cells] contiguous, keep u8 [cells].  For every
+ * element (c, j) with keep[j] != 0, with pin(s) = (1 - s) * x0 + s * noise in icv_add_noise_f32's arithmetic (1 - s formed in f32,
+ * two products, one sum, no fused multiply-add; round_bf16 != 0 rounds all three to bf16):
+ *   latent <- pin(sigma_next);   x_hat <- pin(sigma_cur) if x_hat;   m_new <- x0 if m_new
+ * so with keep == 1 everywhere latent equals icv_add_noise_f32's output bit for bit.  Elements of cells that are not kept are
+ * NOT written.  The keep bytes of a thread's cells are read first; where none is set nothing else is read.  Any C >= 1,
+ * cells >= 1, any keep pointer and any 4-byte-aligned float pointers: 16-byte vectors, each guarded by four keep bytes, where
+ * cells % 4 == 0 and every float tensor sits at the same offset from a 16-byte boundary; element by element before and after
+ * that body and everywhere otherwise.  latent, x_hat and m_new must not overlap x0, noise or each other.  C == 0 or cells == 0
+ * launches nothing; a negative size, a null latent / x0 / noise / keep or a misaligned float pointer is an error. */
+int icv_pin_known_f32(float* latent, float* x_hat, float* m_new, const float* x0, const float* noise, const uint8_t* keep,
+                      int64_t C, int64_t cells, float sigma_next, float sigma_cur, int round_bf16, void* stream);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,20 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ unsigned f32_to_bf16_bits(float f) { return pack_bf16x2(f, 0.f) & 0xffffu; }
 
+// One element of the flow-match noising (1 - sigma) * x + sigma * z, shared by icv_add_noise_f32 (v2v.hip) and icv_pin_known_f32
+// (inpaint.hip), whose results are compared bit for bit against a restatement with one tensor operation per product and one for
+// the sum, in both rounding modes: no fused multiply-add contraction, whatever the including file's setting.
+__device__ __forceinline__ float add_noise_one(float x, float z, float one_minus, float sigma, int round_bf16) {
+#pragma clang fp contract(off)
+  float a = one_minus * x, b = sigma * z;
+  if (round_bf16) {
+    // the three tensors a bf16 pipeline materialises: (1 - sigma) * x0, sigma * noise, their sum
+    auto rb = [](float v) { return bf16_to_f32((bf16_t)f32_to_bf16_bits(v)); };
+    return rb(rb(a) + rb(b));
+  }
+  return a + b;
+}
+
 // Element offset of output (m, n) for the GEMM epilogues: plain [M, N] (nsplit == N) or split planes
 // [N / nsplit][M][nsplit].  A 64-bit n / nsplit per fragment cost more VALU than the GELU; the plain case needs no
 // division at all and the split case only a 32-bit one (N < 2^31 is checked by the dispatchers).

@@ -7,18 +7,9 @@
 #include "icv_common.h"
 
 // No fused multiply-add contraction in this file: the result is compared bit for bit against a restatement with one tensor
-// operation per product and one for the sum, in both rounding modes.
+// operation per product and one for the sum, in both rounding modes.  The element's arithmetic is add_noise_one (icv_common.h),
+// shared with icv_pin_known_f32.
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ float add_noise_one(float x, float z, float one_minus, float sigma, int round_bf16) {
-  float a = one_minus * x, b = sigma * z;
-  if (round_bf16) {
-    // the three tensors a bf16 pipeline materialises: (1 - sigma) * x0, sigma * noise, their sum
-    auto rb = [](float v) { return bf16_to_f32((bf16_t)f32_to_bf16_bits(v)); };
-    return rb(rb(a) + rb(b));
-  }
-  return a + b;
-}
 
 // Threads [0, n_vec): one 16-byte vector each, elements [head + 4 idx, head + 4 idx + 4).  Threads [n_vec, n_vec + n - 4 n_vec):
 // one element each - first the `head` elements in front of the vector body, then the ones behind it.

@@ -116,6 +116,8 @@ SIGNATURES.update({
     "icv_unpatchify_cfg_multistep": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _F, _F, c_int, _F, _F, _F, _F, _F, _F, _F,
                                              _I, _I, _I, _I, _I, _I, c_int, _P]),
     "icv_cfg_zero_scale_f32": (c_int, [_P, _P, _I, _I, _I, _P, _P, c_int, _P]),
+    "icv_latent_keep_mask_u8": (c_int, [_P, _P, _I, _I, _I, _P]),
+    "icv_pin_known_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, c_int, _P]),
 })
 
 class KVPiece(ctypes.Structure):

@@ -1141,7 +1141,7 @@ class WanDiT:
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
                 branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None,
-                guidance=None) -> torch.Tensor:
+                guidance=None, known=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1161,7 +1161,12 @@ class WanDiT:
         (build both over the executed range).  With ``optimized_scale`` every executed step runs icv_cfg_zero_scale_f32 on the two
         head outputs right in front of its update launch, on that launch's stream: s = <c, u> / (|u|^2 + 1e-8) into slot i of a
         device array and ``head_out[1] <- s * head_out[1]`` IN PLACE (nothing reads the unconditional head output after the update).
-        The scales are read back once, after the loop, into ``self.guidance_scales``.  None: today's launches, allocations and bits."""
+        The scales are read back once, after the loop, into ``self.guidance_scales``.  None: today's launches, allocations and bits.
+        ``known`` (inpaint.KnownPlan: the device tensors x0, noise, keep): right after every step's update launch, on its stream, one
+        icv_pin_known_f32 puts the kept cells of ``latent`` back on the known clip's noising trajectory at the next sigma (0 after the
+        last step) - computed and TeaCache-skipped steps alike; under a multistep solver the same launch pins the solver's state, x_hat
+        at this step's sigma and the x0-prediction slot the update just wrote to x0.  Zero-init steps still run nothing; one pin to the
+        first executed step's sigma runs in front of it.  ``on_step`` sees the pinned latent.  None: today's launches and bits."""
         ops, plan = self.ops, self.plan
         self.guidance_scales = None
         windows = sliding_window is not None and len(sliding_window.windows) > 1
@@ -1179,12 +1184,16 @@ class WanDiT:
              options.TEACACHE: tea_cache is not None and "TeaCache (one residual per window and CFG branch is not implemented)"})
         if guidance is not None and guidance.optimized_scale and not (ctx_uncond is not None and cfg_scale != 1.0):
             raise ValueError("cfg_zero_star needs classifier-free guidance (an unconditional context and cfg_scale != 1)")
+        if known is not None:
+            if parallel:
+                raise ValueError(f"denoise: known cells (input_mask) cannot be combined with {parallel} yet")
+            known.check(latent)
         if solver is not None and (len(solver.sigmas) != len(scheduler.sigmas) or any(a != b for a, b in zip(solver.sigmas, scheduler.sigmas))):
             raise ValueError("denoise: the solver plan was not built on this scheduler's sigmas")
         if windows:
             use_cfg = ctx_uncond is not None and cfg_scale != 1.0
             return self._denoise_windows(latent, [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], buf_tokens, scheduler, cfg_scale,
-                                         steps, on_step, round_bf16, sliding_window)
+                                         steps, on_step, round_bf16, sliding_window, known)
         res = self._tc_residuals() if tea_cache is not None else None
         if branch_exchange is not None:
             if (ctx_cond is None) == (ctx_uncond is None) or cfg_scale == 1.0:
@@ -1197,14 +1206,20 @@ class WanDiT:
         gd_scale = guidance is not None and guidance.optimized_scale
         gd_steps = []                                                  # the steps of this call, and whether each one computed a scale
         gd_work = gd_out = None                                        # allocated at the first scaled step, after everything else
+        sigma_after = lambda i: scheduler.sigmas[i + 1] if i + 1 < len(scheduler.sigmas) else 0.0      # noqa: E731
+        repin = False                                                  # zero-init steps were skipped: the kept cells sit at the start sigma
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
             if guidance is not None:
                 if guidance.skips(i):                                  # zero-init: the velocity is zero, so nothing runs
                     gd_steps.append((i, False))
+                    repin = known is not None
                     if on_step is not None:
                         on_step(i, latent)
                     continue
                 gd_steps.append((i, gd_scale))
+            if repin:                                                  # one pin to the first executed step's sigma, in front of it
+                ops.pin_known(latent, known.x0, known.noise, known.keep, scheduler.sigmas[i], round_bf16=round_bf16)
+                repin = False
             ts = scheduler.timesteps[i]
             if res is not None and tea_cache.skip(i):
                 # TeaCache: no blocks, so no K|V exchange either (every rank skips the same steps); both branches on this stream
@@ -1225,9 +1240,14 @@ class WanDiT:
                 ops.unpatchify_cfg_multistep(latent, x_hat, ring[k % 3], ring[(k - 1) % 3], ring[(k - 2) % 3], self.head_out[0],
                                              self.head_out[1] if use_cfg else None, cfg_scale, st.sigma, st.a, st.c,
                                              plan.tok0, plan.n_tok, round_bf16=round_bf16)
+                if known is not None:
+                    ops.pin_known(latent, known.x0, known.noise, known.keep, sigma_after(i), x_hat=x_hat, sigma_cur=st.sigma,
+                                  m_new=ring[k % 3], round_bf16=round_bf16)
             else:
                 ops.unpatchify_cfg_euler(latent, self.head_out[0], self.head_out[1] if use_cfg else None,
                                          cfg_scale, scheduler.dsigma(i), plan.tok0, plan.n_tok, round_bf16=round_bf16)
+                if known is not None:
+                    ops.pin_known(latent, known.x0, known.noise, known.keep, sigma_after(i), round_bf16=round_bf16)
             if self.sp_on:
                 self._check_transport()
             if on_step is not None:
@@ -1256,7 +1276,7 @@ class WanDiT:
         eng.cfg_batch, eng.share_stem, eng.native_forward = self.cfg_batch, self.share_stem, self.native_forward
         return eng
 
-    def _denoise_windows(self, latent, ctxs, buf_tokens, scheduler, cfg_scale, steps, on_step, round_bf16, sw):
+    def _denoise_windows(self, latent, ctxs, buf_tokens, scheduler, cfg_scale, steps, on_step, round_bf16, sw, known=None):
         ops, per_frame = self.ops, self.grid.tokens_per_frame
         C, T, H8, W8 = latent.shape
         if T != sw.T or (H8, W8) != tuple(self.grid.latent_hw):
@@ -1281,6 +1301,9 @@ class WanDiT:
                     ops.unpatchify_cfg_euler_window(nxt, eng.head_out[0], eng.head_out[1] if use_cfg else None, cfg_scale,
                                                     scheduler.dsigma(i), coef[w], f0, 0, (f1 - f0) * per_frame, round_bf16=round_bf16)
                 cur, nxt = nxt, cur
+                if known is not None:                                 # the whole clip's latent, after every window's update
+                    ops.pin_known(cur, known.x0, known.noise, known.keep,
+                                  scheduler.sigmas[i + 1] if i + 1 < len(scheduler.sigmas) else 0.0, round_bf16=round_bf16)
                 if on_step is not None:
                     on_step(i, cur)
         finally:

@@ -485,3 +485,36 @@ class HipOps:
         assert x0.is_contiguous() and noise.is_contiguous() and out.is_contiguous()
         native.check(self.lib.icv_add_noise_f32(x0.data_ptr(), noise.data_ptr(), out.data_ptr(), out.numel(), float(sigma),
                                                 int(bool(round_bf16)), self._stream()), "icv_add_noise_f32")
+
+    # ---- regenerating part of a clip (inpaint.py) -------------------------------------
+    def latent_keep_mask(self, mask_u8, keep_u8):
+        """mask u8 [N, H, W] (non-zero = regenerate) -> keep u8 [(N - 1) / 4 + 1, H / 8, W / 8]: 1 where every mask byte of the
+        cell's stride footprint is 0 (icv_latent_keep_mask_u8)."""
+        _chk(mask_u8, torch.uint8, "latent_keep_mask.mask"); _chk(keep_u8, torch.uint8, "latent_keep_mask.keep")
+        if mask_u8.dim() != 3 or mask_u8.shape[0] % 4 != 1 or mask_u8.shape[1] % 16 or mask_u8.shape[2] % 16:
+            raise ValueError(f"latent_keep_mask: mask must be [4k + 1, H, W] with H and W multiples of 16, got {tuple(mask_u8.shape)}")
+        N, H, W = mask_u8.shape
+        if tuple(keep_u8.shape) != ((N - 1) // 4 + 1, H // 8, W // 8):
+            raise ValueError(f"latent_keep_mask: keep must be {((N - 1) // 4 + 1, H // 8, W // 8)} for a mask of {(N, H, W)}, got {tuple(keep_u8.shape)}")
+        assert mask_u8.is_contiguous() and keep_u8.is_contiguous()
+        native.check(self.lib.icv_latent_keep_mask_u8(mask_u8.data_ptr(), keep_u8.data_ptr(), N, H, W, self._stream()), "icv_latent_keep_mask_u8")
+
+    def pin_known(self, latent, x0, noise, keep, sigma_next: float, x_hat=None, sigma_cur: float = 0.0, m_new=None, round_bf16=False):
+        """Where keep != 0: latent = (1 - sigma_next) * x0 + sigma_next * noise in add_noise's arithmetic, x_hat (if given) the same
+        at sigma_cur, m_new (if given) = x0; other elements are not written (icv_pin_known_f32).  latent, x0, noise, x_hat, m_new
+        f32 [C, ...] of one shape, keep u8 of that shape without the channel dimension."""
+        _chk(latent, F32, "pin_known.latent"); _chk(x0, F32, "pin_known.x0"); _chk(noise, F32, "pin_known.noise")
+        _chk(keep, torch.uint8, "pin_known.keep")
+        if x_hat is not None:
+            _chk(x_hat, F32, "pin_known.x_hat")
+        if m_new is not None:
+            _chk(m_new, F32, "pin_known.m_new")
+        shape = tuple(latent.shape)
+        if len(shape) < 1 or any(tuple(t.shape) != shape for t in (x0, noise, x_hat, m_new) if t is not None):
+            raise ValueError(f"pin_known: latent {shape}, x0 {tuple(x0.shape)}, noise {tuple(noise.shape)}, x_hat and m_new must have one shape")
+        if tuple(keep.shape) != shape[1:]:
+            raise ValueError(f"pin_known: keep must be {shape[1:]} for a latent of {shape}, got {tuple(keep.shape)}")
+        assert all(t.is_contiguous() for t in (latent, x0, noise, keep, x_hat, m_new) if t is not None)
+        native.check(self.lib.icv_pin_known_f32(latent.data_ptr(), native.ptr(x_hat), native.ptr(m_new), x0.data_ptr(), noise.data_ptr(),
+                                                keep.data_ptr(), shape[0], keep.numel(), float(sigma_next), float(sigma_cur),
+                                                int(bool(round_bf16)), self._stream()), "icv_pin_known_f32")

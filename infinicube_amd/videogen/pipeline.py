@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import attn_window, guidance, lora, multigpu, options, sliding_window, solver, teacache, v2v
+from . import attn_window, guidance, inpaint, lora, multigpu, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -269,6 +269,7 @@ class WanVideoPipeline:
         solver.validate(self.sample_solver)
         for name in options.RECORDS.values():    # what the last call did with each feature; lora_record: what is merged now
             setattr(self, name, None)
+        self.inpaint_record = None               # {"cells", "kept_cells", "kept_fraction"} of the last call's input_mask
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
@@ -455,7 +456,7 @@ class WanVideoPipeline:
                  sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
                  sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
-                 cfg_zero_init_steps: Optional[int] = None, **unused):
+                 cfg_zero_init_steps: Optional[int] = None, input_mask=None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -466,6 +467,7 @@ class WanVideoPipeline:
         for feature, name in options.RECORDS.items():
             if feature != options.LORA:              # what is merged outlives a call: _reconcile_lora owns that record
                 setattr(self, name, None)
+        self.inpaint_record = None                   # input_mask is a keyword without an environment route: not an options row
         # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
         # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
         # same bits), the attention window when it does not cover the clip (the same).
@@ -482,6 +484,7 @@ class WanVideoPipeline:
         gd_plan = guidance.validate(opt.cfg_zero_star, opt.cfg_zero_init_steps, num_inference_steps, cfg_scale)
         first_step = gd_plan.zero_init_steps if gd_plan is not None else 0        # the first step that runs: where solver and TeaCache begin
         v2v_frames, strength = v2v.validate(opt.input_video, opt.denoising_strength, num_frames)      # reads the clip (a path)
+        mask = inpaint.validate(input_mask, v2v_frames, num_frames, height, width)    # uint8 [N, H, W], non-zero = regenerate
         world, rank = 1, 0
         try:
             import torch.distributed as dist
@@ -578,7 +581,7 @@ class WanVideoPipeline:
             for vid in vids:
                 if len(vid) != num_frames:
                     raise ValueError(f"buffer video has {len(vid)} frames, num_frames={num_frames}")
-        n_buf = len(vids)
+        n_buf, known = len(vids), None
         if v2v_frames is not None:                    # the input clip rides in the buffers' pass (alone when there are none)
             vids = vids + (v2v_frames,)
         if vids:
@@ -602,7 +605,18 @@ class WanVideoPipeline:
             if self.reference_rounding:
                 x0 = x0.to(torch.bfloat16).to(torch.float32)
             sigma_0 = self.scheduler.sigmas[0]
-            ops.add_noise(ops.to_device(x0, torch.float32), latent, latent, sigma_0, round_bf16=self.reference_rounding)
+            x0 = ops.to_device(x0, torch.float32)
+            if mask is not None:
+                # input_mask: pool the mask to latent cells on the device, read the cells back ONCE for the record;
+                # where any is kept the call holds x0 and a copy of the noise (add_noise overwrites the noise's tensor) for the pins
+                keep = ops.alloc(tuple(latent.shape[1:]), torch.uint8)
+                ops.latent_keep_mask(ops.to_device(torch.from_numpy(mask), torch.uint8), keep)
+                self.inpaint_record = inpaint.record(keep.cpu().numpy())
+                if self.inpaint_record["kept_cells"] > 0:
+                    noise = ops.alloc(tuple(latent.shape), torch.float32)
+                    noise.copy_(latent)
+                    known = inpaint.KnownPlan(x0, noise, keep)
+            ops.add_noise(x0, latent, latent, sigma_0, round_bf16=self.reference_rounding)
             self.v2v_record = dict(denoising_strength=strength, sigma_0=sigma_0)
         if i2v:
             y = self._image_cond_latents(input_image, grid, tiled, tile_size, tile_stride)
@@ -630,7 +644,8 @@ class WanVideoPipeline:
             it = progress_bar_cmd(it)
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
-                       round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan)
+                       round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan,
+                       **(dict(known=known) if known is not None else {}))
         if gd_plan is not None:
             self.guidance_record = gd_plan.record(engine.guidance_scales)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
