@@ -163,6 +163,21 @@ int icv_attn_tile16_lean(bool short_kv) {
   return -1;
 }
 
+// Form of attn7p.hip's key loop around the lean body (icv_set_option("attn7p_slim", n)): 1 = the slim loop (steady intervals without the
+// loop-control tests, their DMA requests from running tile pointers with one M0 write per K or V pair), 0 = the one loop, negative = the
+// default.  Same tiles and requests in the same order: outputs and carried state are bit-identical (tests/test_attn_slim_loop_gpu.py).
+// It applies where the lean body runs (attn_mfma = 16, attn_tile16_lean = 1), to the pieces, chunk and plain launches of attn7p.hip.
+// Default: 1 - every round of the slim arm beat every round of the one loop's at the 14B self-attention (23.27 vs 24.34 ms) and its two
+// shard shapes (interleaved in one process, tools/attn_slim_ab.py; profiles/attn_slim_loop/README.md).
+constexpr int ATTN7P_SLIM_DEFAULT = 1;
+int icv_attn7p_slim() {
+  const int v = icv_get_option_int("attn7p_slim", -1);
+  if (v < 0) return ATTN7P_SLIM_DEFAULT;
+  if (v == 0 || v == 1) return v;
+  icv_set_error("attn7p_slim = %d: 1 = the slim key loop of attn7p, 0 = the one loop; negative = the default", v);
+  return -1;
+}
+
 // ---- diagnostics: where and when every work-group of the NEXT attn7 launches runs -----------------------------------------
 // icv_attention_trace(buf, capacity): buf = device u64 [capacity][4] (NULL switches tracing off).  While set, every attn7
 // work-group b < capacity writes buf[b] = {start, end (s_memrealtime ticks, 100 MHz), HW_ID, XCC_ID} - the round structure and

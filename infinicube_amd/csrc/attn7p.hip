@@ -96,6 +96,31 @@ __device__ __forceinline__ void dma16s(const void* base, unsigned off, unsigned 
       : "memory");
 }
 
+// SLIM: one FULL tile of the ring, this wave's share of it - K pieces j = 0, 1 to lds_dst and lds_dst + 1 KiB, the V pieces TILE_BYTES
+// further on.  M0 is written and read inside the statement and NOT put back (the compiler keeps nothing in it: the clobber says so);
+// the instruction's offset: field moves the LDS address AND the global address, so piece 1 shares piece 0's M0 and its lane offset
+// comes in 1 KiB short (ko1 / vo1: ko[1] / vo[1] of a SLIM kernel).  The s_nop is the wait state between an SALU write of M0 and the
+// LDS-DMA that reads it: the compiler pads nothing inside a string.  Two M0 writes and two wait states per tile, where dma16s has
+// twelve moves and four.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"      // "clobber list contains reserved registers: m0" - reserved, and still to be named
+__device__ __forceinline__ void dma_tile_slim(const void* kt, const void* vt, unsigned ko0, unsigned ko1, unsigned vo0, unsigned vo1,
+                                              unsigned lds_dst) {
+  asm volatile(
+      "s_mov_b32 m0, %6\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %0, %4\n\t"
+      "global_load_lds_dwordx4 %1, %4 offset:1024\n\t"
+      "s_add_u32 m0, %6, %7\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %2, %5\n\t"
+      "global_load_lds_dwordx4 %3, %5 offset:1024"
+      :
+      : "v"(ko0), "v"(ko1), "v"(vo0), "v"(vo1), "s"(kt), "s"(vt), "s"(lds_dst), "i"(TILE_BYTES)
+      : "memory", "m0", "scc");
+}
+#pragma clang diagnostic pop
+
 // uncached (system-scope) dword load WITHOUT a compiler-inserted wait: the caller consumes the value after its own s_waitcnt vmcnt(0)
 __device__ __forceinline__ unsigned load_flag_async(const unsigned* f) {
   unsigned v;
@@ -107,10 +132,18 @@ __device__ __forceinline__ unsigned load_flag_async(const unsigned* f) {
 // MF (option "attn_mfma"): 32 = v_mfma_f32_32x32x16_bf16, the tile below; 16 = v_mfma_f32_16x16x32_bf16 at the same wave tile, ring and
 // softmax: attc::tile16 (attn_common.h, lane maps there), the tile attn7.hip runs at MF = 16 - the two stay bit-identical at either shape
 // LEAN (MF = 16 only, option "attn_tile16_lean", default on): attc::tile16's lean body - K / V fragment addresses formed once and moved with the ring
-template <bool UNIT, bool FW, int MF, bool LEAN = false>
+// SLIM (LEAN only, option "attn7p_slim"): a third form of the key loop.  Every interval whose two tiles and two requested tiles are full
+// tiles of the current piece, with two more intervals of the piece behind it, runs a STEADY body: no last-interval, second-tile, clamp,
+// ragged-tile, tail-mask or poll test, the two requests through dma_tile_slim from running K / V tile pointers and a ring destination
+// that alternates between its two values.  The last intervals of a piece (ragged tile, odd count, the run through a boundary, the
+// poll, a bubble) are the loop below, unchanged.  Same tiles, same requests in the same order between the same barriers, same LDS
+// bytes: outputs and carried state are bit-identical (tests/test_attn_slim_loop_gpu.py).  SLIM stands in front of LEAN so that an
+// instantiation's name still ends in its LEAN value.
+template <bool UNIT, bool FW, int MF, bool SLIM = false, bool LEAN = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7p_kernel(Params pp) {
   static_assert(MF == 16 || MF == 32, "MF: 16 (16x16x32 MFMAs) or 32 (32x32x16)");
   static_assert(MF == 16 || !LEAN, "the lean body is a body of the MF = 16 tile");
+  static_assert(LEAN || !SLIM, "the slim loop is a loop around the lean body");
   const attc::Params& p = pp.a;
   const float p_lim = __builtin_amdgcn_exp2f(p.thr);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -194,8 +227,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     dkey[j] = (wave * NI + j) * 4 + (lane >> 4);
     kcol[j] = (pc ^ (dkey[j] & 15)) * 8;
     vcol[j] = MF == 16 ? attc::tile16_vcol(pc, dkey[j]) : (pc ^ ((dkey[j] & 3) << 2)) * 8;
-    ko[j] = (unsigned)(((int64_t)dkey[j] * p.ldk + kcol[j]) * 2);
-    vo[j] = (unsigned)(((int64_t)dkey[j] * p.ldv + vcol[j]) * 2);
+    // SLIM: piece j's lane offset comes in j KiB short, and its requests make that up in the offset: field (dma_tile_slim) or in the
+    // base (P_DMA_TILE).  It stays >= 0: piece 1 starts at row >= 4 and launch() takes SLIM only for rows of 256 B or more
+    ko[j] = (unsigned)(((int64_t)dkey[j] * p.ldk + kcol[j]) * 2) - (SLIM ? j * 1024u : 0u);
+    vo[j] = (unsigned)(((int64_t)dkey[j] * p.ldv + vcol[j]) * 2) - (SLIM ? j * 1024u : 0u);
   }
 
   // ---- the piece the DMA side reads (wave-uniform) ----
@@ -226,8 +261,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     if ((tt_ + 1) * KVB <= skv_d) {                                                                  \
       const bf16_t* kt_ = kh_d + (int64_t)tt_ * KVB * p.ldk;                                         \
       const bf16_t* vt_ = vh_d + (int64_t)tt_ * KVB * p.ldv;                                         \
-      _Pragma("unroll") for (int j_ = 0; j_ < NI; ++j_) dma16s(kt_, ko[j_], l0_ + j_ * 1024);        \
-      _Pragma("unroll") for (int j_ = 0; j_ < NI; ++j_) dma16s(vt_, vo[j_], l0_ + TILE_BYTES + j_ * 1024); \
+      _Pragma("unroll") for (int j_ = 0; j_ < NI; ++j_) dma16s(kt_ + (SLIM ? j_ * 512 : 0), ko[j_], l0_ + j_ * 1024); \
+      _Pragma("unroll") for (int j_ = 0; j_ < NI; ++j_) dma16s(vt_ + (SLIM ? j_ * 512 : 0), vo[j_], l0_ + TILE_BYTES + j_ * 1024); \
     } else {                                                                                         \
       _Pragma("unroll") for (int j_ = 0; j_ < NI; ++j_) {                                            \
         int64_t r_ = (int64_t)tt_ * KVB + dkey[j_];                                                  \
@@ -406,7 +441,43 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     bool next_ready = has_next && nflag < 0;      // wave-uniform
     bool next_issued = false;
     if (!FW && pp.ptrace && tid == 0) pp.ptrace[(size_t)blockIdx.x * np + pj] = __builtin_amdgcn_s_memrealtime();
-    for (int t = 0; t < nt; t += 2) {
+    int t_steady = 0;                 // SLIM: the first tile the loop below takes
+    if constexpr (SLIM) {
+      int t = 0;
+      // steady intervals: tiles t .. t + 5 are full tiles of this piece, so two intervals of the loop below always follow - the first of
+      // them takes the flag sample that the last one's verdict comes from, as it does without SLIM (a flag, once there, stays)
+      const int t_last = (skv >> 6) - 6;
+      if (t_last >= 0) {
+        const int64_t kstep = (int64_t)KVB * p.ldk, vstep = (int64_t)KVB * p.ldv;     // the DMA piece is this piece (see P_SET_DMA_PIECE's callers)
+        const bf16_t* kt_d = kh_d + 2 * kstep;                                       // tile t + 2
+        const bf16_t* vt_d = vh_d + 2 * vstep;
+        const unsigned l_w = lds_base + (unsigned)(wave * NI * 1024);
+        unsigned l0_d = l_w + (unsigned)(((gt + 2) & (NST - 1)) * STAGE_BYTES);      // gt is even: stage 0 or 2, and the other one next time
+        const unsigned l_sum = 2 * l_w + 2 * STAGE_BYTES;
+        // the second tile stands behind a test the compiler cannot see through (always taken: one s_cmp and one branch per interval).
+        // Without the join behind it the allocator lets the PV accumulators wander (D != C), pads 12 wait states per interval in front
+        // of the LDS reads that reuse a C register, and takes 251 VGPRs at UNIT = false; with it: none, 209 / 197 VGPRs
+        // (profiles/attn_slim_loop/README.md)
+        int yes = 1;
+        asm volatile("" : "+s"(yes));
+        static_assert(NI == 2, "dma_tile_slim issues two K and two V pieces per wave");
+        for (; t <= t_last; t += 2) {
+          dma_tile_slim(kt_d, vt_d, ko[0], ko[1], vo[0], vo[1], l0_d);
+          dma_tile_slim(kt_d + kstep, vt_d + vstep, ko[0], ko[1], vo[0], vo[1], l0_d + STAGE_BYTES);
+          kt_d += 2 * kstep;
+          vt_d += 2 * vstep;
+          l0_d = l_sum - l0_d;
+          tile(std::integral_constant<int, 0>{}, 0, 0, KVB);                        // a full tile: key0 + KVB > skv is false where it is written
+          if (yes) tile(std::integral_constant<int, 1>{}, 0, 0, KVB);
+          attc::tile16_lean_advance(la16, la16_step);
+          la16_step = -la16_step;
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          P_BARRIER();
+        }
+        t_steady = t;
+      }
+    }
+    for (int t = SLIM ? t_steady : 0; t < nt; t += 2) {
       const bool last_iv = t + 2 >= nt;
       if (!last_iv) {                                    // the other half of the ring: last read in the previous interval
         P_DMA_TILE(t + 2, gt + t + 2);
@@ -473,12 +544,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #undef P_WAIT_PIECE
 }
 
-template <bool UNIT, bool FW, int MF, bool LEAN = false>
+template <bool UNIT, bool FW, int MF, bool SLIM = false, bool LEAN = false>
 int launch_mf(const Params& pp, hipStream_t st) {
   static icv_dev_flags attr_set = {};
-  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW, MF, LEAN>, LDS_BYTES, &attr_set, "attn7p")) return rc;
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7p_kernel<UNIT, FW, MF, SLIM, LEAN>, LDS_BYTES, &attr_set, "attn7p")) return rc;
   const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
-  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW, MF, LEAN>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
+  hipLaunchKernelGGL((attn7p_kernel<UNIT, FW, MF, SLIM, LEAN>), dim3((unsigned)nwg), dim3(NW * 64), LDS_BYTES, st, pp);
   return icv_check_launch(FW ? "icv_attention_fwd_framewin" : "icv_attention_fwd_pieces");
 }
 
@@ -490,7 +561,14 @@ int launch(const Params& pp, hipStream_t st) {
   if (mf != 16) return launch_mf<UNIT, FW, 32>(pp, st);
   const int lean = icv_attn_tile16_lean(false);     // body of the MF = 16 tile (option "attn_tile16_lean")
   if (lean < 0) return 1;
-  return lean ? launch_mf<UNIT, FW, 16, true>(pp, st) : launch_mf<UNIT, FW, 16>(pp, st);
+  if (!lean) return launch_mf<UNIT, FW, 16>(pp, st);
+  if constexpr (!FW) {
+    const int slim = icv_attn7p_slim();             // form of the key loop around the lean body (option "attn7p_slim")
+    if (slim < 0) return 1;
+    // dma_tile_slim takes a lane offset 1 KiB short of a row >= 4: rows of 256 B or more, which is every layout but a degenerate one
+    if (slim && pp.a.ldk >= D && pp.a.ldv >= D) return launch_mf<UNIT, FW, 16, true, true>(pp, st);
+  }
+  return launch_mf<UNIT, FW, 16, false, true>(pp, st);
 }
 
 }  // namespace att7p

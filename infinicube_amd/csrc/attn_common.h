@@ -10,6 +10,7 @@
 unsigned long long* icv_attention_trace_buffer(int* capacity);   // attention.hip (icv_attention_trace)
 int icv_attn_mfma(bool short_kv);                                // attention.hip: MFMA shape of attn7 / attn7p (16 or 32; -1 = error set)
 int icv_attn_tile16_lean(bool short_kv);                         // attention.hip: body of the MF = 16 tile (1 = lean, 0 = the first one)
+int icv_attn7p_slim();                                           // attention.hip: attn7p's key loop around the lean body (1 = slim, 0 = the one loop)
 
 namespace attc {
 

@@ -3,8 +3,9 @@ assembly with csrc/build.sh's flags (hipcc -S --cuda-device-only) and read back.
 
 Printed:
   * per kernel instantiation the VGPR count and the scratch size (the .amdhsa metadata: .vgpr_count, .private_segment_fixed_size);
-  * for the default long-key kernel att7p::attn7p_kernel<true, false, 16, LEAN> under each body of the MF = 16 tile (LEAN = false: the
-    first body; true: the lean one, option attn_tile16_lean) the HOT PATH of one iteration of the key loop, by instruction class.  One
+  * for the default long-key kernel att7p::attn7p_kernel<true, false, 16, SLIM, LEAN> under each body of the MF = 16 tile (LEAN = false: the
+    first body; true: the lean one, option attn_tile16_lean) and, third column, under the slim key loop around the lean body (SLIM,
+    option attn7p_slim) the HOT PATH of one iteration of the key loop, by instruction class.  One
     iteration = two 64-key tiles = 128 MFMAs and the DMA requests of the next two (full) tiles.  The hot path is the cheapest walk
     through the loop's blocks from its header back to its header that issues exactly 128 MFMAs and 8 global_load_lds: the re-base
     branches, the tail mask, the ragged-tile DMA and the piece-boundary code all cost instructions and carry no MFMA, so the cheapest
@@ -116,11 +117,13 @@ def count(ins, pattern):
     return sum(1 for x in ins if re.match(pattern, x))
 
 
-def hot_path(blocks):
-    """Instructions of the cheapest header-to-header walk with N_MFMA MFMAs and N_DMA LDS-DMA requests, over every candidate header."""
+def hot_path(blocks, any_back_edge=False):
+    """Instructions of the cheapest header-to-header walk with N_MFMA MFMAs and N_DMA LDS-DMA requests, over every candidate header:
+    every target of a backward conditional branch; any_back_edge: of a backward s_branch as well (the steady loop of the slim form has
+    its last re-base block laid out in front of its header, closes with an s_branch around it and reaches the header by falling through)."""
     succ = successors(blocks)
     cost = [(len(ins), count(ins, "v_mfma"), count(ins, "global_load_lds")) for _, ins in blocks]
-    headers = sorted({t for i, s in enumerate(succ) for t in s if t <= i and blocks[i][1] and blocks[i][1][-1].startswith("s_c")})
+    headers = sorted({t for i, s in enumerate(succ) for t in s if t <= i and blocks[i][1] and re.match(r"s_c?branch" if any_back_edge else r"s_cbranch", blocks[i][1][-1])})
     best = None
     for h in headers:
         start = (cost[h][0], h, cost[h][1], cost[h][2])
@@ -185,27 +188,30 @@ def classify(ins):
     return out
 
 
-def default_kernel(resources, lean):
-    """Mangled name of att7p::attn7p_kernel<true, false, 16, lean> (before the lean body existed: <true, false, 16>)."""
-    want = "ILb1ELb0ELi16ELb%dEEE" % (1 if lean else 0)
-    hits = [n for n in resources if "attn7p_kernel" in n and want in n]
+def default_kernel(resources, lean, slim=False):
+    """Mangled name of att7p::attn7p_kernel<true, false, 16, slim, lean> (before the slim loop existed: <true, false, 16, lean>; before
+    the lean body: <true, false, 16>)."""
+    assert lean or not slim
+    hits = [n for n in resources if "attn7p_kernel" in n and "ILb1ELb0ELi16ELb%dELb%dEEE" % (slim, lean) in n]
+    if not hits and not slim:
+        hits = [n for n in resources if "attn7p_kernel" in n and "ILb1ELb0ELi16ELb%dEEE" % lean in n]
     if not hits and not lean:
         hits = [n for n in resources if "attn7p_kernel" in n and "ILb1ELb0ELi16EEE" in n]
-    assert len(hits) == 1, f"attn7p_kernel<true, false, 16, {lean}>: {hits}"
+    assert len(hits) == 1, f"attn7p_kernel<true, false, 16, {slim}, {lean}>: {hits}"
     return hits[0]
 
 
 def census(outdir):
-    """{"resources": {source: {demangled: {...}}}, "hot": {"first": {...}, "lean": {...}}}"""
+    """{"resources": {source: {demangled: {...}}}, "hot": {"first": {...}, "lean": {...}, "slim": {...}}}"""
     asm = {s: open(p).read() for s, p in compile_all(outdir).items()}
     res, result = {}, {"resources": {}, "hot": {}}
     for s, text in asm.items():
         res[s] = kernel_resources(text)
         names = demangle(list(res[s]))
         result["resources"][s] = {names[n]: r for n, r in res[s].items()}
-    for arm, lean in (("first", False), ("lean", True)):
-        name = default_kernel(res["attn7p"], lean)
-        result["hot"][arm] = classify(hot_path(function_blocks(asm["attn7p"], name)))
+    for arm, lean, slim in (("first", False, False), ("lean", True, False), ("slim", True, True)):
+        name = default_kernel(res["attn7p"], lean, slim)
+        result["hot"][arm] = classify(hot_path(function_blocks(asm["attn7p"], name), any_back_edge=slim))
     return result
 
 
@@ -216,11 +222,12 @@ def report(c):
         for n, r in sorted(c["resources"][s].items()):
             lines.append(f"  vgpr {r['vgpr']:3d}  agpr {r['agpr']:3d}  scratch {r['scratch']:4d} B  {n}")
         lines.append("")
-    lines += ["hot path of one iteration of the key loop (two 64-key tiles, 128 keys) of att7p::attn7p_kernel<true, false, 16, LEAN>",
-              "  first = LEAN false (attn_tile16_lean = 0), lean = LEAN true (attn_tile16_lean = 1)", "",
-              f"  {'instructions per 128 keys':46s} {'first':>6s} {'lean':>6s}"]
+    lines += ["hot path of one iteration of the key loop (two 64-key tiles, 128 keys) of att7p::attn7p_kernel<true, false, 16, SLIM, LEAN>",
+              "  first = LEAN false (attn_tile16_lean = 0), lean = LEAN true (attn_tile16_lean = 1),",
+              "  slim = LEAN and SLIM true (attn7p_slim = 1): the steady interval of the slim key loop", "",
+              f"  {'instructions per 128 keys':46s} {'first':>6s} {'lean':>6s} {'slim':>6s}"]
     for k in c["hot"]["first"]:
-        lines.append(f"  {k:46s} {c['hot']['first'][k]:6d} {c['hot']['lean'][k]:6d}")
+        lines.append(f"  {k:46s} {c['hot']['first'][k]:6d} {c['hot']['lean'][k]:6d} {c['hot']['slim'][k]:6d}")
     return "\n".join(lines) + "\n"
 
 
