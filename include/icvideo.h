@@ -40,7 +40,8 @@ extern "C" {
  *    (video-to-video start latent); icv_attention_fwd_framewin (frame-windowed self-attention in one launch);
  *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms);
  *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output);
- *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step). */
+ *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step);
+ *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -618,6 +619,19 @@ int icv_latent_keep_mask_u8(const uint8_t* mask, uint8_t* keep, int64_t N, int64
  * launches nothing; a negative size, a null latent / x0 / noise / keep or a misaligned float pointer is an error. */
 int icv_pin_known_f32(float* latent, float* x_hat, float* m_new, const float* x0, const float* noise, const uint8_t* keep,
                       int64_t C, int64_t cells, float sigma_next, float sigma_cur, int round_bf16, void* stream);
+
+/* ---- Normalized Attention Guidance: nag_scale ---------------------------------------------------------------
+ * icv_nag_combine_bf16: z_pos, z_neg, out bf16 [rows, d] with leading dimensions ld_* (elements).  Per row, in f32, with p = z_pos
+ * and n = z_neg:
+ *   g = scale * p - (scale - 1) * n   (evaluated as p + (scale - 1) * (p - n): n == p gives g == p exactly)
+ *   Np = sum |p|,  Ng = sum |g|,  c = Ng > tau * Np ? tau * Np / Ng : 1
+ *   out = bf16_rne(alpha * c * g + (1 - alpha) * p)
+ * A row with Np == 0 gives c == 0 and zeros, never a NaN.  Every input byte is read once, before the row's first store: out may
+ * be z_pos (or z_neg) itself with the same leading dimension; any other overlap is the caller's error.  d % 256 == 0 and
+ * d <= 8192 (every such width), leading dimensions multiples of 8 and >= d, 16-byte-aligned pointers, 0 < rows < 2^31; anything
+ * else is an error and launches nothing.  The columns [d, ld) of a row are neither read nor written. */
+int icv_nag_combine_bf16(const void* z_pos, int64_t ld_pos, const void* z_neg, int64_t ld_neg, void* out, int64_t ld_out,
+                         int64_t rows, int64_t d, float scale, float tau, float alpha, void* stream);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,7 @@ SIGNATURES.update({
     "icv_cfg_zero_scale_f32": (c_int, [_P, _P, _I, _I, _I, _P, _P, c_int, _P]),
     "icv_latent_keep_mask_u8": (c_int, [_P, _P, _I, _I, _I, _P]),
     "icv_pin_known_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, c_int, _P]),
+    "icv_nag_combine_bf16": (c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _F, _P]),
 })
 
 class KVPiece(ctypes.Structure):

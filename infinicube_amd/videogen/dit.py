@@ -84,6 +84,7 @@ class _Branch:
     ctx: ContextKV
     kv_full: Optional[torch.Tensor] = None    # sequence parallel: where its gathered K|V rows land
     kv8: Optional[tuple] = None               # ... and its e4m3 wire set (_sp_wire_set)
+    nag: Optional[object] = None              # nag.NagPlan: its text cross-attention also runs against the negative context
 
 
 class WanDiT:
@@ -357,6 +358,9 @@ class WanDiT:
         # CFG-Zero* (guidance.py): (fp64 partial-sum workspace, f32 [N] scales of a call's steps), allocated on first use;
         # guidance_scales: the last guided call's scale per step (None for a step that computed none), None without guidance
         self._guidance_state, self.guidance_scales = None, None
+        # Normalized Attention Guidance (nag.py): the plan of the denoise call that is running (None outside one and without NAG)
+        # and the second attention-output buffer, bf16 [n, d], allocated on first use
+        self._nag, self._nag_buf = None, None
         # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
         # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
         self._lat_tok0, self._win_engines, self._win_next = None, {}, None
@@ -599,6 +603,7 @@ class WanDiT:
     # Frame-windowed self-attention (attn_window.py).  None = dense.  The setting lives on the engine that was prepared;
     # the 2n-row pair engine reads it from there (_blocks), the dual-stream twin is handed it per step.
     attn_window = None
+    _nag, _nag_buf = None, None        # Normalized Attention Guidance: the running call's plan, the second attention-output buffer (prepare())
 
     def set_attention_window(self, window=None, sink=None):
         """Self-attention of every layer reads, per query, only the latent frames within ``window`` of the query's own plus the first
@@ -629,8 +634,9 @@ class WanDiT:
                                    and not self.fp8_wire and not self.attn_arrival)
         # ... and it patchifies from token 0 of the latent: a sliding window starts at a frame offset, so the per-op driver runs
         # ... and its self-attention is dense (the frame-windowed launch is driven per op)
+        # ... and its cross-attention is one launch per layer (Normalized Attention Guidance adds two)
         return (self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok and self._lat_tok0 is None
-                and self._framewin() is None)
+                and self._framewin() is None and self._nag is None)
 
     def native_profile(self, enable: bool):
         """Time every self-attention launch of the native forward with HIP events on the launch stream (bench.py)."""
@@ -871,8 +877,10 @@ class WanDiT:
         if self._graphs_on:
             # a window's offset into the latent is an argument of the captured patchify: part of the key
             # ... and so is the attention window: another launch with other scalars
+            # ... and so is Normalized Attention Guidance: two more launches per layer, the negative context and three scalars
+            nag = self._nag
             key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem, self._lat_tok0,
-                   self._framewin())
+                   self._framewin(), None if nag is None else (id(nag.ctx_neg),) + nag.key)
             entry = self._graphs.get(key)
             if entry is None:
                 # first call with these buffers: run eagerly (that IS this call's result; it also lets every kernel do
@@ -882,7 +890,7 @@ class WanDiT:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     self._forward_body(latent, ctx, buf_tokens, head_out, num_layers, stem)
-                self._graphs[key] = (g, ctx, latent, buf_tokens, head_out)   # keep the captured buffers alive
+                self._graphs[key] = (g, ctx, latent, buf_tokens, head_out, nag)   # keep the captured buffers alive
             else:
                 entry[0].replay()
             return
@@ -908,7 +916,7 @@ class WanDiT:
                 ki.stride(0) if ki is not None else 0, native.ptr(buf_tokens), head_out.data_ptr(),
                 -1 if num_layers is None else num_layers, {None: 0, "save": 1, "load": 2}[stem], self.attn_scale, ops._stream()), "icv_dit_forward")
             return
-        branch = _Branch(slice(0, self.plan.n_tok), ctx, self.kv_full, self.kv8)
+        branch = _Branch(slice(0, self.plan.n_tok), ctx, self.kv_full, self.kv8, self._nag)
         if stem == "load":
             self.x.copy_(self.x_stem)          # the residual stream after layer 0's self-attention block (see forward_tokens)
         else:
@@ -997,6 +1005,10 @@ class WanDiT:
             ops.rmsnorm_rope(q, lw["xnq"], eps=eps)
             for b, qb, _, _, ab in views:
                 ops.attention(qb, b.ctx.k[i], b.ctx.v[i], ab, H, scale)
+                if b.nag is not None:                                                                         # NAG: the same queries against the negative text
+                    neg, an = b.nag.ctx_neg, self._nag_rows(t)[b.rows]
+                    ops.attention(qb, neg.k[i], neg.v[i], an, H, scale)
+                    ops.nag_combine(ab, an, ab, b.nag.scale, b.nag.tau, b.nag.alpha)
                 if b.ctx.k_img is not None:                                                                   # i2v: + softmax over CLIP tokens
                     ops.attention_add(qb, b.ctx.k_img[i], b.ctx.v_img[i], ab, H, scale)
             a = t._operand(t.att, t.att8, t.att8s, lw["xo_w"])
@@ -1029,6 +1041,7 @@ class WanDiT:
         t._lat_tok0, t._win_engines, t._win_next = None, {}, None
         t._solver_state = None
         t._guidance_state, t.guidance_scales = None, None
+        t._nag, t._nag_buf = None, None
         return t
 
     def _pair_engine(self):
@@ -1101,6 +1114,13 @@ class WanDiT:
             self._guidance_state = (self.ops.alloc((CFG_ZERO_WORKSPACE_DOUBLES,), torch.float64), self.ops.alloc((n_steps,), F32))
         return self._guidance_state
 
+    @staticmethod
+    def _nag_rows(t):
+        """The second attention-output buffer of workspace ``t`` (the negative text's softmax), bf16 like ``t.att``: first use only."""
+        if t._nag_buf is None:
+            t._nag_buf = t.ops.alloc(tuple(t.att.shape), BF16)
+        return t._nag_buf
+
     def _tc_store(self, patches: torch.Tensor, x: torch.Tensor, r: torch.Tensor):
         """r = x - (patches @ patch_w.T + patch_b): the residual of a computed forward whose stream ended in ``x``."""
         self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
@@ -1141,7 +1161,7 @@ class WanDiT:
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
                 branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None,
-                guidance=None, known=None) -> torch.Tensor:
+                guidance=None, known=None, nag=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1166,9 +1186,15 @@ class WanDiT:
         icv_pin_known_f32 puts the kept cells of ``latent`` back on the known clip's noising trajectory at the next sigma (0 after the
         last step) - computed and TeaCache-skipped steps alike; under a multistep solver the same launch pins the solver's state, x_hat
         at this step's sigma and the x0-prediction slot the update just wrote to x0.  Zero-init steps still run nothing; one pin to the
-        first executed step's sigma runs in front of it.  ``on_step`` sees the pinned latent.  None: today's launches and bits."""
+        first executed step's sigma runs in front of it.  ``on_step`` sees the pinned latent.  None: today's launches and bits.
+        ``nag`` (nag.NagPlan, Normalized Attention Guidance): the ONE forward of a step (cfg_scale must be 1) runs every layer's text
+        cross-attention a second time against ``nag.ctx_neg`` into a second bf16 [n, d] buffer and combines the two outputs in place
+        (icv_nag_combine_bf16) in front of the CLIP-token softmax of an image-to-video DiT and of cross_attn.o.  The per-op driver
+        runs (the C driver does not know the launches); a captured graph is keyed on the plan.  None: today's launches,
+        allocations and bits."""
         ops, plan = self.ops, self.plan
         self.guidance_scales = None
+        self._nag = None
         windows = sliding_window is not None and len(sliding_window.windows) > 1
         parallel = (self.sp_on or plan.world > 1 or branch_exchange is not None) and "sequence / CFG-branch parallelism (world > 1)"
         options.check_scope(
@@ -1184,6 +1210,14 @@ class WanDiT:
              options.TEACACHE: tea_cache is not None and "TeaCache (one residual per window and CFG branch is not implemented)"})
         if guidance is not None and guidance.optimized_scale and not (ctx_uncond is not None and cfg_scale != 1.0):
             raise ValueError("cfg_zero_star needs classifier-free guidance (an unconditional context and cfg_scale != 1)")
+        if nag is not None:
+            if cfg_scale != 1.0 or ctx_cond is None:
+                raise ValueError("denoise: Normalized Attention Guidance (nag=) runs on the single conditional forward: pass ctx_cond and cfg_scale=1")
+            if parallel:
+                raise ValueError(f"denoise: Normalized Attention Guidance (nag=) cannot be combined with {parallel} yet")
+            if windows:
+                raise ValueError("denoise: Normalized Attention Guidance (nag=) cannot be combined with more than one sliding temporal window yet")
+            self._check_inputs(buf_tokens, nag.ctx_neg)
         if known is not None:
             if parallel:
                 raise ValueError(f"denoise: known cells (input_mask) cannot be combined with {parallel} yet")
@@ -1194,6 +1228,17 @@ class WanDiT:
             use_cfg = ctx_uncond is not None and cfg_scale != 1.0
             return self._denoise_windows(latent, [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], buf_tokens, scheduler, cfg_scale,
                                          steps, on_step, round_bf16, sliding_window, known)
+        self._nag = nag                        # read by _forward_body, _native_eligible and the graph key while the loop runs
+        try:
+            return self._denoise_loop(latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange,
+                                      round_bf16, tea_cache, solver, guidance, known)
+        finally:
+            self._nag = None
+
+    def _denoise_loop(self, latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange, round_bf16,
+                      tea_cache, solver, guidance, known):
+        """denoise() behind its checks: the loop over one window."""
+        ops, plan = self.ops, self.plan
         res = self._tc_residuals() if tea_cache is not None else None
         if branch_exchange is not None:
             if (ctx_cond is None) == (ctx_uncond is None) or cfg_scale == 1.0:

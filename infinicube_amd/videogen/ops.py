@@ -420,6 +420,20 @@ class HipOps:
         native.check(self.lib.icv_cfg_zero_scale_f32(hc.data_ptr(), hu.data_ptr(), hc.stride(0), n_tok, hc.shape[1], workspace.data_ptr(),
                                                      scale_out.data_ptr(), int(bool(round_bf16)), self._stream()), "icv_cfg_zero_scale_f32")
 
+    def nag_combine(self, zp, zn, out, scale, tau, alpha):
+        """Normalized Attention Guidance (nag.py): zp, zn, out bf16 [rows, d] (row strides allowed); per row, in f32,
+        g = scale * zp - (scale - 1) * zn, c = min(|g|_1 / |zp|_1, tau) / (|g|_1 / |zp|_1), out = alpha * c * g + (1 - alpha) * zp
+        (icv_nag_combine_bf16: the row stays in registers, so ``out`` may be ``zp`` itself)."""
+        _chk(zp, BF16, "nag_combine.zp"); _chk(zn, BF16, "nag_combine.zn"); _chk(out, BF16, "nag_combine.out")
+        if zp.dim() != 2 or tuple(zn.shape) != tuple(zp.shape) or tuple(out.shape) != tuple(zp.shape):
+            raise ValueError(f"nag_combine: zp, zn and out must be [rows, d] of one shape, got {tuple(zp.shape)}, {tuple(zn.shape)}, {tuple(out.shape)}")
+        rows, d = zp.shape
+        if rows == 0 or d % 256 or d > 8192 or any(t.stride(0) % 8 or t.data_ptr() % 16 for t in (zp, zn, out)):
+            raise ValueError(f"nag_combine: needs rows > 0, d % 256 == 0 and d <= 8192 (got {rows} x {d}), row strides that are multiples "
+                             "of 8 and 16-byte-aligned rows")
+        native.check(self.lib.icv_nag_combine_bf16(zp.data_ptr(), zp.stride(0), zn.data_ptr(), zn.stride(0), out.data_ptr(), out.stride(0),
+                                                   rows, d, float(scale), float(tau), float(alpha), self._stream()), "icv_nag_combine_bf16")
+
     def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
         """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
         window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import attn_window, guidance, inpaint, lora, multigpu, options, sliding_window, solver, teacache, v2v
+from . import attn_window, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -270,6 +270,10 @@ class WanVideoPipeline:
         for name in options.RECORDS.values():    # what the last call did with each feature; lora_record: what is merged now
             setattr(self, name, None)
         self.inpaint_record = None               # {"cells", "kept_cells", "kept_fraction"} of the last call's input_mask
+        # Normalized Attention Guidance (nag.py): attributes behind the keywords of the same names, no environment route; with
+        # cfg_scale = 1 the negative prompt acts inside the one forward of a step.  nag_record: {"scale", "tau", "alpha"} of the last call
+        self.nag_scale = self.nag_tau = self.nag_alpha = None
+        self.nag_record = None
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
@@ -456,7 +460,8 @@ class WanVideoPipeline:
                  sliding_window_stride: Optional[int] = None, input_video=None, denoising_strength: Optional[float] = None,
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
                  sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
-                 cfg_zero_init_steps: Optional[int] = None, input_mask=None, **unused):
+                 cfg_zero_init_steps: Optional[int] = None, input_mask=None, nag_scale: Optional[float] = None,
+                 nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -468,6 +473,7 @@ class WanVideoPipeline:
             if feature != options.LORA:              # what is merged outlives a call: _reconcile_lora owns that record
                 setattr(self, name, None)
         self.inpaint_record = None                   # input_mask is a keyword without an environment route: not an options row
+        self.nag_record = None                       # ... and so are nag_scale / nag_tau / nag_alpha (keyword, else attribute)
         # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
         # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
         # same bits), the attention window when it does not cover the clip (the same).
@@ -485,6 +491,8 @@ class WanVideoPipeline:
         first_step = gd_plan.zero_init_steps if gd_plan is not None else 0        # the first step that runs: where solver and TeaCache begin
         v2v_frames, strength = v2v.validate(opt.input_video, opt.denoising_strength, num_frames)      # reads the clip (a path)
         mask = inpaint.validate(input_mask, v2v_frames, num_frames, height, width)    # uint8 [N, H, W], non-zero = regenerate
+        nag_on = nag.validate(*(getattr(self, n) if kw is None else kw for n, kw in
+                                (("nag_scale", nag_scale), ("nag_tau", nag_tau), ("nag_alpha", nag_alpha))))      # (scale, tau, alpha) | None
         world, rank = 1, 0
         try:
             import torch.distributed as dist
@@ -506,6 +514,8 @@ class WanVideoPipeline:
              options.I2V: self.dit.cfg.has_image_input and "an image-to-video DiT (the first-frame conditioning belongs to window 0 only)",
              options.TEACACHE: opt.tea_cache_l1_thresh is not None and "TeaCache (tea_cache_l1_thresh / ICV_TEACACHE_L1_THRESH) in the same call",
              options.FP8_ATTN: self.attn_dtype == "fp8" and "the e4m3 self-attention mode (torch_dtype=float8_e4m3fn)"})
+        if nag_on is not None:
+            nag.check_call(cfg_scale, world, windows)
         engine = self._get_engine()
         ops = engine.ops
         tc_thresh, tc_id = teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, engine.cfg,
@@ -554,6 +564,10 @@ class WanVideoPipeline:
             ctx_c = engine.encode_context(self.text_encoder.encode(prompt), clip_fea)
         if cfg_scale != 1.0 and layout.branch in (None, 1):
             ctx_u = engine.encode_context(self.text_encoder.encode(negative_prompt), clip_fea)
+        nag_plan = None
+        if nag_on is not None:                        # cfg_scale == 1: the negative prompt acts inside the one forward of a step
+            nag_plan = nag.NagPlan(engine.encode_context(self.text_encoder.encode(negative_prompt), clip_fea), *nag_on)
+            self.nag_record = nag_plan.record()
         # noise: CPU generator, fp32 (rand_device='cpu' upstream) -> identical across devices/ranks
         g = torch.Generator(device="cpu")
         if seed is None:
@@ -645,7 +659,7 @@ class WanVideoPipeline:
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
                        round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan,
-                       **(dict(known=known) if known is not None else {}))
+                       **(dict(known=known) if known is not None else {}), **(dict(nag=nag_plan) if nag_plan is not None else {}))
         if gd_plan is not None:
             self.guidance_record = gd_plan.record(engine.guidance_scales)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
