@@ -41,7 +41,8 @@ extern "C" {
  *    icv_unpatchify_cfg_multistep (multistep samplers: the fused latent update as two linear forms);
  *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output);
  *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step);
- *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output). */
+ *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output);
+ *    icv_enhance_scores_bf16 and icv_enhance_apply_bf16 (Enhance-A-Video: the cross-frame attention boost of a self-attention output). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -632,6 +633,30 @@ int icv_pin_known_f32(float* latent, float* x_hat, float* m_new, const float* x0
  * else is an error and launches nothing.  The columns [d, ld) of a row are neither read nor written. */
 int icv_nag_combine_bf16(const void* z_pos, int64_t ld_pos, const void* z_neg, int64_t ld_neg, void* out, int64_t ld_out,
                          int64_t rows, int64_t d, float scale, float tau, float alpha, void* stream);
+
+/* ---- Enhance-A-Video: enhance_weight --------------------------------------------------------------------------
+ * One self-attention call on a token grid of T latent frames x P positions, token (t, s) in row t * P + s; q, k bf16
+ * [T * P, heads * 128] with leading dimensions ldq, ldk (elements) - the operands of icv_attention_fwd.  Per position s and head h,
+ * in f32:
+ *   L[t, t'] = scale * sum_c q[(t, s), h, c] * k[(t', s), h, c]        A[t, .] = softmax over t' of L[t, .]  (max-subtracted)
+ *   m[s, h]  = (sum over t != t' of A[t, t']) / (T (T - 1))
+ *   E        = max(1, (T + weight) * mean over (s, h) of m[s, h])
+ * icv_enhance_scores_bf16 leaves one partial sum per position (the sum over h and t of the off-diagonal mass of A's row t) in
+ * workspace[0 .. P) - one work-group per position, whatever the shape - and, where score_out is not NULL, E in score_out[0] from a
+ * second one-group launch.  Rows of the 32-frame tile at or beyond T, rows beyond T * P and columns beyond heads * 128 are not read.
+ * icv_enhance_apply_bf16 (att bf16 [rows, d], leading dimension ld): every work-group adds the P partials in one fixed order (fp64),
+ * forms E, and replaces its share of att by bf16_rne(f32(att) * E) in 16-byte vectors; group 0 stores E to score_out[0].  E == 1
+ * leaves att as it is (x * 1 == x).  Columns [d, ld) of a row are neither read nor written.  No atomics, no host read: the same
+ * inputs give the same bits.
+ * Errors, nothing launched: T outside [2, 32] (one 32-frame tile; longer clips are sliding-window calls), a head width other than
+ * 128 (ldq, ldk < heads * 128), leading dimensions that are not multiples of 8, q / k / att not 16-byte aligned, P above
+ * ICV_ENHANCE_WORKSPACE_FLOATS or heads above 65535, a negative or non-finite weight, scale <= 0, d % 8 != 0, rows or d outside
+ * [1, 2^31). */
+#define ICV_ENHANCE_WORKSPACE_FLOATS 16384
+int icv_enhance_scores_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, int64_t T, int64_t P, int64_t heads, float scale,
+                            float weight, float* workspace, float* score_out, void* stream);
+int icv_enhance_apply_bf16(void* att, int64_t ld, int64_t rows, int64_t d, const float* workspace, int64_t T, int64_t P, int64_t heads,
+                           float weight, float* score_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,7 @@ class _Branch:
     kv_full: Optional[torch.Tensor] = None    # sequence parallel: where its gathered K|V rows land
     kv8: Optional[tuple] = None               # ... and its e4m3 wire set (_sp_wire_set)
     nag: Optional[object] = None              # nag.NagPlan: its text cross-attention also runs against the negative context
+    slot: int = 0                             # which CFG branch it is (0 = cond): its row of the Enhance-A-Video factor buffer
 
 
 class WanDiT:
@@ -361,6 +362,10 @@ class WanDiT:
         # Normalized Attention Guidance (nag.py): the plan of the denoise call that is running (None outside one and without NAG)
         # and the second attention-output buffer, bf16 [n, d], allocated on first use
         self._nag, self._nag_buf = None, None
+        # Enhance-A-Video (enhance.py): the plan of the denoise call that is running, the CFG branch forward_tokens runs, the
+        # per-position partial sums of this workspace (f32 [P]) and the factors E (f32 [2, L]), both allocated on first use;
+        # enhance_scores: E per layer per branch of the last enhanced call's last computed forward (host, read back once per call)
+        self._enhance, self._enhance_slot, self._enhance_ws, self._enhance_E, self.enhance_scores = None, 0, None, None, None
         # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
         # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
         self._lat_tok0, self._win_engines, self._win_next = None, {}, None
@@ -604,6 +609,7 @@ class WanDiT:
     # the 2n-row pair engine reads it from there (_blocks), the dual-stream twin is handed it per step.
     attn_window = None
     _nag, _nag_buf = None, None        # Normalized Attention Guidance: the running call's plan, the second attention-output buffer (prepare())
+    _enhance, _enhance_slot, _enhance_ws, _enhance_E, enhance_scores = None, 0, None, None, None      # Enhance-A-Video (prepare())
 
     def set_attention_window(self, window=None, sink=None):
         """Self-attention of every layer reads, per query, only the latent frames within ``window`` of the query's own plus the first
@@ -635,8 +641,9 @@ class WanDiT:
         # ... and it patchifies from token 0 of the latent: a sliding window starts at a frame offset, so the per-op driver runs
         # ... and its self-attention is dense (the frame-windowed launch is driven per op)
         # ... and its cross-attention is one launch per layer (Normalized Attention Guidance adds two)
+        # ... and nothing sits between its self-attention and the O projection (Enhance-A-Video adds two launches)
         return (self.native_forward and self._is_gpu() and hasattr(self.ops, "lib") and sp_ok and self._lat_tok0 is None
-                and self._framewin() is None and self._nag is None)
+                and self._framewin() is None and self._nag is None and self._enhance is None)
 
     def native_profile(self, enable: bool):
         """Time every self-attention launch of the native forward with HIP events on the launch stream (bench.py)."""
@@ -878,9 +885,11 @@ class WanDiT:
             # a window's offset into the latent is an argument of the captured patchify: part of the key
             # ... and so is the attention window: another launch with other scalars
             # ... and so is Normalized Attention Guidance: two more launches per layer, the negative context and three scalars
-            nag = self._nag
+            # ... and so is Enhance-A-Video: two more launches per layer with the weight and the branch's row of the factor buffer
+            nag, enh = self._nag, self._enhance
             key = (id(ctx), latent.data_ptr(), 0 if buf_tokens is None else buf_tokens.data_ptr(), head_out.data_ptr(), num_layers, stem, self._lat_tok0,
-                   self._framewin(), None if nag is None else (id(nag.ctx_neg),) + nag.key)
+                   self._framewin(), None if nag is None else (id(nag.ctx_neg),) + nag.key,
+                   None if enh is None else enh.key + (self._enhance_slot,))
             entry = self._graphs.get(key)
             if entry is None:
                 # first call with these buffers: run eagerly (that IS this call's result; it also lets every kernel do
@@ -916,7 +925,7 @@ class WanDiT:
                 ki.stride(0) if ki is not None else 0, native.ptr(buf_tokens), head_out.data_ptr(),
                 -1 if num_layers is None else num_layers, {None: 0, "save": 1, "load": 2}[stem], self.attn_scale, ops._stream()), "icv_dit_forward")
             return
-        branch = _Branch(slice(0, self.plan.n_tok), ctx, self.kv_full, self.kv8, self._nag)
+        branch = _Branch(slice(0, self.plan.n_tok), ctx, self.kv_full, self.kv8, self._nag, self._enhance_slot)
         if stem == "load":
             self.x.copy_(self.x_stem)          # the residual stream after layer 0's self-attention block (see forward_tokens)
         else:
@@ -954,6 +963,10 @@ class WanDiT:
         q, k, v = t.qkv[0], t.qkv[1], t.qkv[2]
         views = [(b, q[b.rows], k[b.rows], v[b.rows], t.att[b.rows]) for b in branches]      # once per forward, not per layer
         fw = self._framewin()                                # frame-windowed self-attention: (window, sink) | None
+        enh = self._enhance                                  # Enhance-A-Video: the plan | None
+        if enh is not None:
+            eT, eP = self.grid.T, self.grid.tokens_per_frame
+            ews, eE = self._enhance_buffers(t)
         for i in range(L):
             lw = self.layers[i]
             m = self.mod[i]
@@ -987,7 +1000,7 @@ class WanDiT:
                     else:   # some of the rows of each plane: three plain GEMMs keep the [3, rows, d] plane layout
                         for j in range(3):
                             t._mm(h, lw["wqkv"], lw["bqkv"], t.qkv[j][rs], EPI_BF16, rows=slice(j * d, (j + 1) * d))
-                    for _, qb, kb, vb, ab in active:
+                    for b, qb, kb, vb, ab in active:
                         ops.rmsnorm_rope(qb, lw["nq"], kb, lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)  # K5
                         if fw is not None:
                             ops.attention_framewin(qb, kb, vb, ab, H, scale, self.grid.T, self.grid.tokens_per_frame, *fw)   # K6 (windowed)
@@ -995,6 +1008,9 @@ class WanDiT:
                             ops.attention_fp8(qb, kb, vb, ab, H, self.attn8_ws)                               # K6 (e4m3)
                         else:
                             ops.attention(qb, kb, vb, ab, H, scale)                                           # K6
+                        if enh is not None:      # Enhance-A-Video: the cross-frame share of this branch's attention scales its output
+                            ops.enhance_scores(qb, kb, eT, eP, H, scale, enh.weight, ews)
+                            ops.enhance_apply(ab, ews, eT, eP, H, enh.weight, eE[b.slot, i:i + 1])
                 a = t._operand(t.att, t.att8, t.att8s, lw["wo"], rows=rs)
                 t._mm(a, lw["wo"], lw["bo"], xs, EPI_RESID_F32, resid=xs, gate=g1)                            # K7
             if i == 0 and after_stem is not None:
@@ -1042,6 +1058,7 @@ class WanDiT:
         t._solver_state = None
         t._guidance_state, t.guidance_scales = None, None
         t._nag, t._nag_buf = None, None
+        t._enhance, t._enhance_slot, t._enhance_ws, t._enhance_E, t.enhance_scores = None, 0, None, None, None
         return t
 
     def _pair_engine(self):
@@ -1071,7 +1088,7 @@ class WanDiT:
         self._check_inputs(buf_tokens, ctx_c, ctx_u)
         self._time_state(timestep)
         t = self._pair_engine()
-        branches = [_Branch(slice(bi * n, (bi + 1) * n), ctx, t.kv_full[bi] if self.sp_on else None, t.kv8[bi] if t.kv8 is not None else None)
+        branches = [_Branch(slice(bi * n, (bi + 1) * n), ctx, t.kv_full[bi] if self.sp_on else None, t.kv8[bi] if t.kv8 is not None else None, slot=bi)
                     for bi, ctx in enumerate((ctx_c, ctx_u))]
         first, second = t.x[branches[0].rows], t.x[branches[1].rows]
         self._patch_embed(latent, buf_tokens, first)      # K1 once: both branches start from the same tokens
@@ -1121,6 +1138,16 @@ class WanDiT:
             t._nag_buf = t.ops.alloc(tuple(t.att.shape), BF16)
         return t._nag_buf
 
+    def _enhance_buffers(self, t):
+        """(partial sums f32 [P] of workspace ``t``, factors f32 [2, L] of this engine) of Enhance-A-Video: first use only.  The
+        factors start as NaN: a row that still holds them after a call saw no computed forward."""
+        if t._enhance_ws is None:
+            t._enhance_ws = t.ops.alloc((self.grid.tokens_per_frame,), F32)
+        if self._enhance_E is None:
+            self._enhance_E = self.ops.alloc((2, max(self.cfg.num_layers, 1)), F32)
+            self._enhance_E.fill_(float("nan"))
+        return t._enhance_ws, self._enhance_E
+
     def _tc_store(self, patches: torch.Tensor, x: torch.Tensor, r: torch.Tensor):
         """r = x - (patches @ patch_w.T + patch_b): the residual of a computed forward whose stream ended in ``x``."""
         self.ops.gemm(patches, self.patch_w, self.patch_b, r, EPI_F32)
@@ -1138,6 +1165,9 @@ class WanDiT:
             # filled by the other branch's kernels
             twin, side = self._cfg_twin()
             twin._lat_tok0, twin.attn_window = self._lat_tok0, self.attn_window
+            if self._enhance is not None:      # the twin's blocks write row 1 of THIS engine's factor buffer, with partial sums of their own
+                self._enhance_buffers(self)
+            twin._enhance, twin._enhance_slot, twin._enhance_E = self._enhance, 1, self._enhance_E
             main = torch.cuda.current_stream(self.ops.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -1154,14 +1184,16 @@ class WanDiT:
         else:
             share = pair and self.share_stem
             for b, (ctx, out) in enumerate(zip(ctxs, outs)):
+                self._enhance_slot = b
                 self.forward_tokens(latent, ctx, ts, buf_tokens, out, stem=("save", "load")[b] if share else None)
+                self._enhance_slot = 0
                 yield b, self.patches, self.x
 
     def denoise(self, latent: torch.Tensor, ctx_cond: Optional[ContextKV], ctx_uncond: Optional[ContextKV],
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
                 branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None,
-                guidance=None, known=None, nag=None) -> torch.Tensor:
+                guidance=None, known=None, nag=None, enhance=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1191,10 +1223,16 @@ class WanDiT:
         cross-attention a second time against ``nag.ctx_neg`` into a second bf16 [n, d] buffer and combines the two outputs in place
         (icv_nag_combine_bf16) in front of the CLIP-token softmax of an image-to-video DiT and of cross_attn.o.  The per-op driver
         runs (the C driver does not know the launches); a captured graph is keyed on the plan.  None: today's launches,
-        allocations and bits."""
+        allocations and bits.
+        ``enhance`` (enhance.EnhancePlan, Enhance-A-Video): in every layer and for every CFG branch, between self-attention and the O
+        projection, icv_enhance_scores_bf16 measures the cross-frame share of the branch's attention on its q / k and
+        icv_enhance_apply_bf16 scales its attention output by E = max(1, (T + weight) * mean) in place; E stays on the device, in
+        an f32 [2, L] buffer that is read back once after the loop (``self.enhance_scores``: E per layer per branch of the last
+        computed forward).  The per-op driver runs; a captured graph is keyed on the weight.  None: today's launches, allocations
+        and bits."""
         ops, plan = self.ops, self.plan
         self.guidance_scales = None
-        self._nag = None
+        self._nag, self._enhance, self._enhance_slot, self.enhance_scores = None, None, 0, None
         windows = sliding_window is not None and len(sliding_window.windows) > 1
         parallel = (self.sp_on or plan.world > 1 or branch_exchange is not None) and "sequence / CFG-branch parallelism (world > 1)"
         options.check_scope(
@@ -1218,6 +1256,14 @@ class WanDiT:
             if windows:
                 raise ValueError("denoise: Normalized Attention Guidance (nag=) cannot be combined with more than one sliding temporal window yet")
             self._check_inputs(buf_tokens, nag.ctx_neg)
+        if enhance is not None:
+            if parallel:
+                raise ValueError(f"denoise: Enhance-A-Video (enhance=) cannot be combined with {parallel} yet")
+            if windows:
+                raise ValueError("denoise: Enhance-A-Video (enhance=) cannot be combined with more than one sliding temporal window yet")
+            from . import enhance as enhance_mod
+            enhance_mod.validate(enhance.weight)
+            enhance_mod.check_frames(self.grid.T, "denoise: Enhance-A-Video (enhance=)")
         if known is not None:
             if parallel:
                 raise ValueError(f"denoise: known cells (input_mask) cannot be combined with {parallel} yet")
@@ -1229,11 +1275,26 @@ class WanDiT:
             return self._denoise_windows(latent, [ctx_cond, ctx_uncond][: 2 if use_cfg else 1], buf_tokens, scheduler, cfg_scale,
                                          steps, on_step, round_bf16, sliding_window, known)
         self._nag = nag                        # read by _forward_body, _native_eligible and the graph key while the loop runs
+        self._enhance = enhance                # ... and so is this, by _blocks too
+        if enhance is not None and self._enhance_E is not None:
+            self._enhance_E.fill_(float("nan"))
         try:
-            return self._denoise_loop(latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange,
-                                      round_bf16, tea_cache, solver, guidance, known)
+            out = self._denoise_loop(latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange,
+                                     round_bf16, tea_cache, solver, guidance, known)
+            if enhance is not None and self._enhance_E is not None:
+                self.enhance_scores = self._enhance_read(2 if ctx_cond is not None and ctx_uncond is not None and cfg_scale != 1.0 else 1)
+            return out
         finally:
-            self._nag = None
+            self._nag, self._enhance, self._enhance_slot = None, None, 0
+
+    def _enhance_read(self, branches: int):
+        """E per layer per branch of the call's last computed forward: the ONE read of the factor buffer, after the loop.  Layer 0 of
+        a branch that took the shared stem has the stem branch's E (its rows were scaled before they were copied).  None: no forward
+        of the call ran the blocks."""
+        vals = self._enhance_E[:branches, :self.cfg.num_layers].cpu()
+        if branches == 2 and vals.shape[1] and bool(torch.isnan(vals[1, 0])):
+            vals[1, 0] = vals[0, 0]
+        return None if vals.numel() == 0 or bool(torch.isnan(vals).any()) else vals.tolist()
 
     def _denoise_loop(self, latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange, round_bf16,
                       tea_cache, solver, guidance, known):

@@ -165,6 +165,9 @@ class WanVideoGenerator:
             from . import nag          # attributes without an options row: the ranks would never see them
             if nag.validate(*(getattr(self.pipe, n, None) for n in ("nag_scale", "nag_tau", "nag_alpha"))) is not None:
                 raise ValueError("pipe.nag_scale cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
+            from . import enhance
+            if enhance.validate(getattr(self.pipe, "enhance_weight", None)) is not None:
+                raise ValueError("pipe.enhance_weight cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -434,6 +434,52 @@ class HipOps:
         native.check(self.lib.icv_nag_combine_bf16(zp.data_ptr(), zp.stride(0), zn.data_ptr(), zn.stride(0), out.data_ptr(), out.stride(0),
                                                    rows, d, float(scale), float(tau), float(alpha), self._stream()), "icv_nag_combine_bf16")
 
+    def enhance_scores(self, q, k, frames: int, frame_rows: int, heads: int, scale: float, weight: float, workspace, score_out=None):
+        """Enhance-A-Video (enhance.py): q, k bf16 [frames * frame_rows, heads * 128] (row strides allowed), the operands of
+        ``attention``.  Per position and head the frames x frames softmax of scale * <q, k> over the frames of that position; the
+        off-diagonal mass of every position goes to ``workspace`` (f32 [>= frame_rows], contiguous) for ``enhance_apply``
+        (icv_enhance_scores_bf16).  ``score_out`` (f32, one element): also E = max(1, (frames + weight) * mean)."""
+        _chk(q, BF16, "enhance_scores.q"); _chk(k, BF16, "enhance_scores.k"); _chk(workspace, F32, "enhance_scores.workspace")
+        rows = frames * frame_rows
+        if q.dim() != 2 or tuple(k.shape) != tuple(q.shape) or q.shape[0] != rows or q.shape[1] != heads * 128:
+            raise ValueError(f"enhance_scores: q and k must be [{frames} frames * {frame_rows} rows, {heads} heads * 128], got "
+                             f"{tuple(q.shape)}, {tuple(k.shape)}")
+        if not 2 <= frames <= 32:
+            raise ValueError(f"enhance_scores: needs 2 <= frames <= 32, got {frames}")
+        if any(t.stride(0) % 8 or t.data_ptr() % 16 for t in (q, k)):
+            raise ValueError("enhance_scores: needs row strides that are multiples of 8 and 16-byte-aligned rows")
+        self._enhance_buffers(workspace, score_out, frame_rows, "enhance_scores")
+        native.check(self.lib.icv_enhance_scores_bf16(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), frames, frame_rows, heads, float(scale),
+                                                      float(weight), workspace.data_ptr(), native.ptr(score_out), self._stream()),
+                     "icv_enhance_scores_bf16")
+
+    def enhance_apply(self, att, workspace, frames: int, frame_rows: int, heads: int, weight: float, score_out):
+        """att bf16 [rows, d] (row stride allowed) <- bf16(f32(att) * E) in place, E = max(1, (frames + weight) * mean) from the partial
+        sums ``enhance_scores`` left in ``workspace``, added up in every block in one fixed order; E -> ``score_out`` (f32, one element)
+        (icv_enhance_apply_bf16)."""
+        _chk(att, BF16, "enhance_apply.att"); _chk(workspace, F32, "enhance_apply.workspace")
+        if att.dim() != 2 or att.shape[0] == 0 or att.shape[1] % 8 or att.stride(0) % 8 or att.data_ptr() % 16:
+            raise ValueError(f"enhance_apply: att must be [rows > 0, d % 8 == 0] with a row stride that is a multiple of 8 and 16-byte-aligned "
+                             f"rows, got {tuple(att.shape)}")
+        if not 2 <= frames <= 32:
+            raise ValueError(f"enhance_apply: needs 2 <= frames <= 32, got {frames}")
+        if score_out is None:
+            raise ValueError("enhance_apply: score_out must be an f32 tensor of one element")
+        self._enhance_buffers(workspace, score_out, frame_rows, "enhance_apply")
+        native.check(self.lib.icv_enhance_apply_bf16(att.data_ptr(), att.stride(0), att.shape[0], att.shape[1], workspace.data_ptr(), frames,
+                                                     frame_rows, heads, float(weight), score_out.data_ptr(), self._stream()),
+                     "icv_enhance_apply_bf16")
+
+    @staticmethod
+    def _enhance_buffers(workspace, score_out, frame_rows, who):
+        if not 0 < frame_rows <= native.ENHANCE_WORKSPACE_FLOATS or workspace.numel() < frame_rows or not workspace.is_contiguous():
+            raise ValueError(f"{who}: workspace must hold one contiguous float per position ({frame_rows}; at most "
+                             f"{native.ENHANCE_WORKSPACE_FLOATS} positions per frame)")
+        if score_out is not None:
+            _chk(score_out, F32, f"{who}.score_out")
+            if score_out.numel() != 1:
+                raise ValueError(f"{who}: score_out must be an f32 tensor of one element")
+
     def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
         """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
         window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import attn_window, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
+from . import attn_window, enhance, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -274,6 +274,10 @@ class WanVideoPipeline:
         # cfg_scale = 1 the negative prompt acts inside the one forward of a step.  nag_record: {"scale", "tau", "alpha"} of the last call
         self.nag_scale = self.nag_tau = self.nag_alpha = None
         self.nag_record = None
+        # Enhance-A-Video (enhance.py): the attribute behind the keyword of the same name, no environment route; every layer's
+        # self-attention output is scaled by its cross-frame share.  enhance_record: {"weight", "frames", "scores"} of the last call
+        self.enhance_weight = None
+        self.enhance_record = None
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
@@ -461,7 +465,7 @@ class WanVideoPipeline:
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
                  sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
                  cfg_zero_init_steps: Optional[int] = None, input_mask=None, nag_scale: Optional[float] = None,
-                 nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, **unused):
+                 nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, enhance_weight: Optional[float] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -474,6 +478,7 @@ class WanVideoPipeline:
                 setattr(self, name, None)
         self.inpaint_record = None                   # input_mask is a keyword without an environment route: not an options row
         self.nag_record = None                       # ... and so are nag_scale / nag_tau / nag_alpha (keyword, else attribute)
+        self.enhance_record = None                   # ... and enhance_weight
         # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
         # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
         # same bits), the attention window when it does not cover the clip (the same).
@@ -493,6 +498,7 @@ class WanVideoPipeline:
         mask = inpaint.validate(input_mask, v2v_frames, num_frames, height, width)    # uint8 [N, H, W], non-zero = regenerate
         nag_on = nag.validate(*(getattr(self, n) if kw is None else kw for n, kw in
                                 (("nag_scale", nag_scale), ("nag_tau", nag_tau), ("nag_alpha", nag_alpha))))      # (scale, tau, alpha) | None
+        enhance_on = enhance.validate(self.enhance_weight if enhance_weight is None else enhance_weight)      # weight | None
         world, rank = 1, 0
         try:
             import torch.distributed as dist
@@ -516,6 +522,8 @@ class WanVideoPipeline:
              options.FP8_ATTN: self.attn_dtype == "fp8" and "the e4m3 self-attention mode (torch_dtype=float8_e4m3fn)"})
         if nag_on is not None:
             nag.check_call(cfg_scale, world, windows)
+        if enhance_on is not None:
+            enhance.check_call(world, windows, grid.T)
         engine = self._get_engine()
         ops = engine.ops
         tc_thresh, tc_id = teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, engine.cfg,
@@ -568,6 +576,7 @@ class WanVideoPipeline:
         if nag_on is not None:                        # cfg_scale == 1: the negative prompt acts inside the one forward of a step
             nag_plan = nag.NagPlan(engine.encode_context(self.text_encoder.encode(negative_prompt), clip_fea), *nag_on)
             self.nag_record = nag_plan.record()
+        enhance_plan = enhance.EnhancePlan(enhance_on) if enhance_on is not None else None
         # noise: CPU generator, fp32 (rand_device='cpu' upstream) -> identical across devices/ranks
         g = torch.Generator(device="cpu")
         if seed is None:
@@ -659,7 +668,10 @@ class WanVideoPipeline:
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
                        round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan,
-                       **(dict(known=known) if known is not None else {}), **(dict(nag=nag_plan) if nag_plan is not None else {}))
+                       **(dict(known=known) if known is not None else {}), **(dict(nag=nag_plan) if nag_plan is not None else {}),
+                       **(dict(enhance=enhance_plan) if enhance_plan is not None else {}))
+        if enhance_plan is not None:
+            self.enhance_record = enhance_plan.record(engine.grid.T, engine.enhance_scores)
         if gd_plan is not None:
             self.guidance_record = gd_plan.record(engine.guidance_scales)
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
