@@ -42,7 +42,8 @@ extern "C" {
  *    icv_cfg_zero_scale_f32 (CFG-Zero* guidance: the optimised scale of the unconditional head output);
  *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step);
  *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output);
- *    icv_enhance_scores_bf16 and icv_enhance_apply_bf16 (Enhance-A-Video: the cross-frame attention boost of a self-attention output). */
+ *    icv_enhance_scores_bf16 and icv_enhance_apply_bf16 (Enhance-A-Video: the cross-frame attention boost of a self-attention output);
+ *    icv_attention_fwd_radial (radial self-attention in one launch: every frame in reach, bands that halve with the distance). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -260,6 +261,22 @@ int icv_attention_fwd_pieces(const void* q, int64_t ldq, const icv_kv_piece* pie
 int icv_attention_fwd_framewin(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                void* o, int64_t ldo, int64_t frames, int64_t frame_rows, int64_t heads,
                                int64_t window, int64_t sink, float scale, void* stream);
+/* Radial self-attention in ONE launch (csrc/attn7r.hip): the operands, leading-dimension and size rules of
+ * icv_attention_fwd_framewin, and frames <= ICV_ATTN_MAX_PIECES.  Every key frame stays in reach; the band of in-frame rows a query
+ * block reads of it halves with every doubling of the temporal distance.  Work-groups are (head, frame f, block of 256 rows of that
+ * frame); with the block's in-frame rows [p0, p1), p1 = min(frame_rows, p0 + 256), it reads of key frame g the in-frame rows
+ *   g < sink or |g - f| <= window: [0, frame_rows);
+ *   otherwise, with e = |g - f| - window, l = floor(log2 e) + 1, h = frame_rows >> (l + 1) (may be 0):
+ *                                  [max(0, p0 - h), min(frame_rows, p1 + h)), never empty,
+ * for g ascending; two ranges that are adjacent in memory are one piece (at most `frames` pieces per work-group, starting and ending at
+ * arbitrary rows).  Each work-group derives its pieces from these scalars (no table in memory, no flags, no host read) and walks them
+ * as icv_attention_fwd_pieces walks pieces that are in place (same tiles, same order, ragged tails masked, softmax state in registers
+ * across all pieces): a work-group's rows are bit-identical to icv_attention_fwd_pieces on those rows with those pieces.
+ * window >= frames - 1 is dense attention and runs icv_attention_fwd.  bf16, the 16x16x32 lean tile, at either scale convention.
+ * Replaces: one icv_attention_fwd_pieces launch per (frame, block); the reference attends densely (Radial Attention [EXT]). */
+int icv_attention_fwd_radial(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                             void* o, int64_t ldo, int64_t frames, int64_t frame_rows, int64_t heads,
+                             int64_t window, int64_t sink, float scale, void* stream);
 /* flags[index] <- value with a system-scope release, enqueued on `stream` (one thread): the arrival flag of a piece whose rows were
  * delivered by something `stream` has waited for (an RCCL collective, a copy); delay_us > 0 first holds the stream for that long
  * (tests: a late peer). */

@@ -107,6 +107,7 @@ SIGNATURES.update({
     "icv_attention_fwd_pieces": (c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _I, _I, c_float, _P, _P, _I, _P, _P]),
     "icv_flag_write": (c_int, [_P, _I, ctypes.c_uint32, _I, _P]),
     "icv_attention_fwd_framewin": (c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, c_float, _P]),
+    "icv_attention_fwd_radial": (c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, c_float, _P]),
     "icv_dit_profile": (c_int, [c_void_p, c_int]),
     "icv_dit_profile_read": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     "icv_sub_rows_f32": (c_int, [_P, _I, _P, _I, _I, _I, _P]),

@@ -608,20 +608,26 @@ class WanDiT:
     # Frame-windowed self-attention (attn_window.py).  None = dense.  The setting lives on the engine that was prepared;
     # the 2n-row pair engine reads it from there (_blocks), the dual-stream twin is handed it per step.
     attn_window = None
+    attn_radial = False                # radial attention: the window is the dense run of a radial mask
     _nag, _nag_buf = None, None        # Normalized Attention Guidance: the running call's plan, the second attention-output buffer (prepare())
     _enhance, _enhance_slot, _enhance_ws, _enhance_E, enhance_scores = None, 0, None, None, None      # Enhance-A-Video (prepare())
 
-    def set_attention_window(self, window=None, sink=None):
+    def set_attention_window(self, window=None, sink=None, radial=False):
         """Self-attention of every layer reads, per query, only the latent frames within ``window`` of the query's own plus the first
-        ``sink`` frames (ONE icv_attention_fwd_framewin launch per layer and branch).  None = dense attention (the default)."""
+        ``sink`` frames (ONE icv_attention_fwd_framewin launch per layer and branch).  None = dense attention (the default).
+        ``radial``: every other frame stays in reach through a band of in-frame rows that halves with every doubling of the temporal
+        distance (attn_window.radial_ranges; ONE icv_attention_fwd_radial launch per layer and branch)."""
         from . import attn_window
-        self.attn_window = attn_window.validate(window, sink)
+        aw = attn_window.validate(window, sink)
+        radial = attn_window.validate_radial(radial, None if aw is None else aw[0])
+        self.attn_window, self.attn_radial = aw, radial
         self._framewin()                                   # a combination that is out of scope raises here when the grid is known
         return self
 
     def _framewin(self):
-        """(window, sink) when the prepared grid's self-attention runs frame-windowed; None when the setting is off or the window
-        covers the whole clip (every range is [0, T): the plain launch, same bits as without the setting)."""
+        """(window, sink) when the prepared grid's self-attention runs frame-windowed, (window, sink, True) when it runs radial; None
+        when the setting is off or the window covers the whole clip (every range is [0, T): the plain launch, same bits as without
+        the setting)."""
         from . import attn_window
         aw = self.attn_window
         grid = getattr(self, "grid", None)
@@ -630,6 +636,9 @@ class WanDiT:
         options.check_scope({options.ATTN_WINDOW: "attention_window_frames"},
                             {options.PARALLEL: self.sp_on and "sequence parallelism (world > 1)",
                              options.FP8_ATTN: self.attn_fp8 and "the e4m3 self-attention mode (attn_dtype='fp8')"})
+        if self.attn_radial:
+            attn_window.validate_radial(True, aw[0], grid.T)          # more frames than a work-group walks pieces raise
+            return aw[0], min(aw[1], grid.T), True
         return aw[0], min(aw[1], grid.T)
 
     def _native_eligible(self) -> bool:
@@ -962,7 +971,7 @@ class WanDiT:
         d, H, eps, scale = cfg.dim, cfg.num_heads, cfg.eps, self.attn_scale      # scale = ln 2: K already carries (1/sqrt(hd)) * log2(e)
         q, k, v = t.qkv[0], t.qkv[1], t.qkv[2]
         views = [(b, q[b.rows], k[b.rows], v[b.rows], t.att[b.rows]) for b in branches]      # once per forward, not per layer
-        fw = self._framewin()                                # frame-windowed self-attention: (window, sink) | None
+        fw = self._framewin()                                # frame-windowed self-attention: (window, sink[, radial]) | None
         enh = self._enhance                                  # Enhance-A-Video: the plan | None
         if enh is not None:
             eT, eP = self.grid.T, self.grid.tokens_per_frame
@@ -1003,7 +1012,8 @@ class WanDiT:
                     for b, qb, kb, vb, ab in active:
                         ops.rmsnorm_rope(qb, lw["nq"], kb, lw["nk"], eps=eps, rope=self.rope, tok0=plan.tok0)  # K5
                         if fw is not None:
-                            ops.attention_framewin(qb, kb, vb, ab, H, scale, self.grid.T, self.grid.tokens_per_frame, *fw)   # K6 (windowed)
+                            (ops.attention_radial if len(fw) == 3 else ops.attention_framewin)(
+                                qb, kb, vb, ab, H, scale, self.grid.T, self.grid.tokens_per_frame, *fw[:2])              # K6 (windowed | radial)
                         elif self.attn8_ws is not None:
                             ops.attention_fp8(qb, kb, vb, ab, H, self.attn8_ws)                               # K6 (e4m3)
                         else:
@@ -1164,7 +1174,7 @@ class WanDiT:
             # (same weights, own workspace), so the partial last wave of blocks of every kernel of one branch is
             # filled by the other branch's kernels
             twin, side = self._cfg_twin()
-            twin._lat_tok0, twin.attn_window = self._lat_tok0, self.attn_window
+            twin._lat_tok0, twin.attn_window, twin.attn_radial = self._lat_tok0, self.attn_window, self.attn_radial
             if self._enhance is not None:      # the twin's blocks write row 1 of THIS engine's factor buffer, with partial sums of their own
                 self._enhance_buffers(self)
             twin._enhance, twin._enhance_slot, twin._enhance_E = self._enhance, 1, self._enhance_E

@@ -364,6 +364,20 @@ class HipOps:
             q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), o.data_ptr(), o.stride(0),
             frames, frame_rows, heads, window, sink, scale, self._stream()), "icv_attention_fwd_framewin")
 
+    def attention_radial(self, q, k, v, o, heads: int, scale: float, frames: int, frame_rows: int, window: int, sink: int):
+        """K6, radial (csrc/attn7r.hip; the rule: attn_window.radial_ranges): ONE launch in which a 256-row query block
+        of latent frame f reads every key frame - whole within ``window`` of f and for the first ``sink`` frames, else a band of
+        in-frame rows around its own that halves with every doubling of the temporal distance."""
+        for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+            _chk(t, BF16, f"attention_radial.{nm}")
+        rows = frames * frame_rows
+        if not (q.shape[0] == k.shape[0] == v.shape[0] == rows and o.shape[0] >= rows):
+            raise ValueError(f"attention_radial: {frames} frames of {frame_rows} rows, but q / k / v / o have "
+                             f"{q.shape[0]} / {k.shape[0]} / {v.shape[0]} / {o.shape[0]} rows")
+        native.check(self.lib.icv_attention_fwd_radial(
+            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), o.data_ptr(), o.stride(0),
+            frames, frame_rows, heads, window, sink, scale, self._stream()), "icv_attention_fwd_radial")
+
     def flag_write(self, flags, index: int, value: int, delay_us: int = 0, stream: Optional[int] = None):
         """flags[index] <- value (system-scope release) on ``stream`` (default: the current one), optionally after holding it delay_us."""
         assert flags.dtype in (torch.int32, torch.uint32) and flags.is_contiguous()

@@ -278,6 +278,10 @@ class WanVideoPipeline:
         # self-attention output is scaled by its cross-frame share.  enhance_record: {"weight", "frames", "scores"} of the last call
         self.enhance_weight = None
         self.enhance_record = None
+        # Radial attention (attn_window.py): the attribute behind the keyword of the same name, no environment route;
+        # True turns attention_window_frames / attention_sink_frames into the dense run and the anchor of a radial mask.  The call's
+        # attention_window_record then carries "radial": True, "key_fraction" in rows and "max_pieces"
+        self.attention_radial = None
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
@@ -465,7 +469,8 @@ class WanVideoPipeline:
                  attention_window_frames: Optional[int] = None, attention_sink_frames: Optional[int] = None,
                  sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
                  cfg_zero_init_steps: Optional[int] = None, input_mask=None, nag_scale: Optional[float] = None,
-                 nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, enhance_weight: Optional[float] = None, **unused):
+                 nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, enhance_weight: Optional[float] = None,
+                 attention_radial: Optional[bool] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -489,6 +494,8 @@ class WanVideoPipeline:
         else:
             sw_plan = None
         aw = attn_window.validate(opt.attention_window_frames, opt.attention_sink_frames, grid.T)
+        radial = attn_window.validate_radial(self.attention_radial if attention_radial is None else attention_radial,
+                                             opt.attention_window_frames, grid.T)      # keyword, else attribute; no options row
         if aw is not None and attn_window.dense(grid.T, aw[0]):
             aw = None
         solver_name = solver.validate(opt.sample_solver)
@@ -553,9 +560,10 @@ class WanVideoPipeline:
         else:
             engine.prepare(grid, plan, group=layout.sp_group, sp_chunks=sp_chunks, kv_exchange=kv_exchange if layout.sp_world > 1 else None)
         if aw is not None or engine.attn_window is not None:
-            engine.set_attention_window(*(aw or (None, None)))
+            engine.set_attention_window(*(aw or (None, None)), radial=radial and aw is not None)
         if aw is not None:
-            self.attention_window_record = attn_window.record(grid.T, *aw)
+            self.attention_window_record = (attn_window.radial_record(grid.T, grid.tokens_per_frame, *aw) if radial
+                                            else attn_window.record(grid.T, *aw))
         self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding, denoising_strength=strength)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
         i2v = engine.cfg.has_image_input
