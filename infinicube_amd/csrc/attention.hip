@@ -178,6 +178,44 @@ int icv_attn7p_slim() {
   return -1;
 }
 
+// attn7p.hip's staggered long-key kernel (icv_set_option("attn7p_stagger", n)): 1 = a launch that takes the slim loop with ONE piece
+// whose rows are there when it starts (the plain launch and the carried-state chunk launches on long keys, a one-piece pieces launch
+// without a flag) runs att7p::attn7ps_kernel - the two waves of a SIMD in opposite phases of the tile, one barrier per 64 keys; 0 = the
+// slim loop; negative = the default.  Same arithmetic in the same order per wave: outputs and carried state are bit-identical
+// (tests/test_attn_stagger_gpu.py).  Multi-piece and flagged launches, the frame-windowed and radial kernels are not touched by it.
+// Two compile-time variants of that kernel, kept for the A/B (tools/attn_stagger_ab.py):
+//   "attn7p_stagger_swap": which half of the work-group opens a slot with the softmax (barrier behind QK^T) and which with the QK^T
+//     MFMAs (barrier behind PV): 1 = waves 0-3 the softmax, waves 4-7 the MFMAs; 0 = the other way round;
+//   "attn7p_stagger_setprio": 1 = s_setprio 1 over softmax + PV, as the tile has it everywhere else, 0 = none.
+// Defaults (interleaved in one process, 9 rounds of 0.45 s, tools/attn_stagger_ab.py; profiles/attn_stagger/README.md):
+// attn7p_stagger_swap = 1 with attn7p_stagger_setprio = 1 is the one combination of which every round beat every round of the slim loop
+// at the 14B self-attention and its two shard shapes; the other three tie with the slim loop.
+constexpr int ATTN7P_STAGGER_DEFAULT = 1;
+constexpr int ATTN7P_STAGGER_SETPRIO_DEFAULT = 1;
+constexpr int ATTN7P_STAGGER_SWAP_DEFAULT = 1;
+int icv_attn7p_stagger() {
+  const int v = icv_get_option_int("attn7p_stagger", -1);
+  if (v < 0) return ATTN7P_STAGGER_DEFAULT;
+  if (v == 0 || v == 1) return v;
+  icv_set_error("attn7p_stagger = %d: 1 = the staggered long-key kernel of attn7p, 0 = the slim loop; negative = the default", v);
+  return -1;
+}
+int icv_attn7p_stagger_setprio() {
+  const int v = icv_get_option_int("attn7p_stagger_setprio", -1);
+  if (v < 0) return ATTN7P_STAGGER_SETPRIO_DEFAULT;
+  if (v == 0 || v == 1) return v;
+  icv_set_error("attn7p_stagger_setprio = %d: 1 = s_setprio over softmax + PV in the staggered kernel, 0 = none; negative = the default", v);
+  return -1;
+}
+
+int icv_attn7p_stagger_swap() {
+  const int v = icv_get_option_int("attn7p_stagger_swap", -1);
+  if (v < 0) return ATTN7P_STAGGER_SWAP_DEFAULT;
+  if (v == 0 || v == 1) return v;
+  icv_set_error("attn7p_stagger_swap = %d: 1 = waves 0-3 open a slot with the softmax and waves 4-7 with QK^T, 0 = the other way round; negative = the default", v);
+  return -1;
+}
+
 // ---- diagnostics: where and when every work-group of the NEXT attn7 launches runs -----------------------------------------
 // icv_attention_trace(buf, capacity): buf = device u64 [capacity][4] (NULL switches tracing off).  While set, every attn7
 // work-group b < capacity writes buf[b] = {start, end (s_memrealtime ticks, 100 MHz), HW_ID, XCC_ID} - the round structure and

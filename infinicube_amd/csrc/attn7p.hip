@@ -544,6 +544,215 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
 #undef P_WAIT_PIECE
 }
 
+// STAGGERED long-key kernel (option "attn7p_stagger"; profiles/attn_stagger/README.md): ONE piece that is there when the launch starts
+// (flag < 0), the lean body of the 16x16x32 tile cut in two (attc::tile16_qk, attc::tile16_sv) and the slim loop's DMA requests.  The
+// two waves of a SIMD - wave w and wave w + 4 - run in OPPOSITE phases of the tile, so that one is in its 32 exps while the other is in
+// a 32-MFMA run: in attn7p_kernel every wave leaves every barrier into the same QK^T MFMAs and meets its partner again at the exps,
+// where the matrix pipe has nothing to do.  (The STAGGER bit of attn1 / 2 / 4 / 7 / 8 delays waves 4-7 by a WHOLE tile, the period of
+// the work: the partners are back in phase, on different tiles.)  Every wave still executes QK(0) SV(0) QK(1) SV(1) ... on its own rows
+// with the arithmetic of tile16's lean body, so outputs and carried state are bit-identical to attn7p_kernel's
+// (tests/test_attn_stagger_gpu.py); only the barriers and the DMA issue are placed differently.  nt tiles, nt + 1 slots, a barrier
+// between two slots (nt barriers per wave); tile t lives in ring stage t & 3; slot h is
+//     group A:  QK(h) SV(h)                      (nothing in slot nt)
+//     group B:  SV(h - 1) QK(h), st carried across the barrier       (QK(0) only in slot 0, SV(nt - 1) only in slot nt)
+// SWAP (option "attn7p_stagger_swap"): false = waves 0-3 are A and waves 4-7 B, true = waves 0-3 are B and waves 4-7 A.  true is the
+// default and what won: the older half (waves 0-3), whose VALU issue the arbiter favours, opens its slot with the softmax and the
+// younger half opens it with MFMAs, which issue at full rate behind a barrier for either (20.79 vs 21.33 ms of the slim loop at the 14B
+// self-attention, interleaved; false: 21.34 - 21.60 ms, a tie, with LESS VALU / MFMA co-execution than the slim loop has).
+// INVARIANTS OF THE RING
+//   (1) Slot h reads K of tile h (A and B), V of tile h (A) and V of tile h - 1 (B): stages h & 3 and (h - 1) & 3.
+//   (2) At the START of slot h every wave requests its share (2 K + 2 V requests) of tile h + 2, if there is one, into stage
+//       (h + 2) & 3 = the stage of tile h - 2, whose K was last read in slot h - 2 and whose V in slot h - 1 (B): both behind the
+//       barrier that ended slot h - 1, and every wave drains lgkmcnt in front of a barrier.  No request goes to a stage of (1).
+//   (3) A slot ends with s_waitcnt vmcnt(4) + barrier when it requested a tile and vmcnt(0) + barrier when it did not: requests retire
+//       in order and the key loop issues no other vector memory instruction, so behind the wait this wave's four requests of tile
+//       h + 1 have landed (only tile h + 2's four may be in flight: LDS-DMA survives s_barrier), and behind the barrier every wave's.
+//       Tile h + 1 is what slot h + 1 reads first; tile h landed one barrier earlier.  Tiles 0 and 1 are requested in front of slot 0
+//       and waited for together.
+//   (4) A ragged last tile takes four requests per wave as a full one does (rows clamped to the last one), so (3) counts the same.
+//   (5) A and B execute the same number of barriers (one per slot 0 .. nt - 1) and the same requests in the same slots; B's SV(nt - 1)
+//       behind the last barrier reads a tile that landed two barriers earlier, and nothing is requested behind it.
+// Cost against attn7p_kernel: one barrier per 64 keys instead of one per 128.  PRIO (option "attn7p_stagger_setprio"): s_setprio 1 over
+// softmax + PV, as tile16 has it - with SWAP it is what makes the difference (21.56 ms without).
+template <bool UNIT, bool PRIO, bool SWAP>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn7ps_kernel(Params pp) {
+  const attc::Params& p = pp.a;
+  const float p_lim = __builtin_amdgcn_exp2f(p.thr);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  int head, qb;
+  attc::work_item(p, head, qb);
+  const int64_t q0 = (int64_t)qb * QB + wave * 32;
+  const unsigned long long t_start = p.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+
+  // ---- softmax state, reference and Q fragments of the wave's two 16-row q-blocks (registers) ----
+  attc::Tile16 s16;
+  int64_t qr16[2];
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    const int64_t r = q0 + qb * 16 + (lane & 15);
+    qr16[qb] = r < p.Sq ? r : p.Sq - 1;
+  }
+  attc::tile16_init<UNIT>(p, qr16, head, lane >> 4, s16);
+  attc::tile16_load_q(p, qr16, head, lane >> 4, s16);
+  __builtin_amdgcn_s_waitcnt(0x0F70);     // retire the VGPR-destination loads before any LDS-DMA is in flight: invariant (3) counts requests only
+
+  // ---- LDS-DMA lane mapping (attn7p_kernel's, SLIM: piece 1's lane offset comes in 1 KiB short) ----
+  static_assert(NI == 2, "dma_tile_slim issues two K and two V pieces per wave");
+  const int pc = lane & 15;
+  const unsigned lds_base = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+  int dkey[NI], kcol[NI], vcol[NI];
+  unsigned ko[NI], vo[NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    dkey[j] = (wave * NI + j) * 4 + (lane >> 4);
+    kcol[j] = (pc ^ (dkey[j] & 15)) * 8;
+    vcol[j] = attc::tile16_vcol(pc, dkey[j]);
+    ko[j] = (unsigned)(((int64_t)dkey[j] * p.ldk + kcol[j]) * 2) - j * 1024u;
+    vo[j] = (unsigned)(((int64_t)dkey[j] * p.ldv + vcol[j]) * 2) - j * 1024u;
+  }
+  const bf16_t* kh = pp.piece[0].k + (int64_t)head * D;
+  const bf16_t* vh = pp.piece[0].v + (int64_t)head * D;
+  const int skv = __builtin_amdgcn_readfirstlane(pp.piece[0].rows);
+  const int nt = (skv + KVB - 1) / KVB;
+  __builtin_assume(nt >= 1);
+  const int64_t kstep = (int64_t)KVB * p.ldk, vstep = (int64_t)KVB * p.ldv;
+  const unsigned l_w = lds_base + (unsigned)(wave * NI * 1024);
+  // this wave's share of tile T_ (< nt) -> stage T_ & 3: four requests, ragged or not
+  auto dma_tile = [&](const int t) __attribute__((always_inline)) {
+    const unsigned l0 = l_w + (unsigned)((t & (NST - 1)) * STAGE_BYTES);
+    if ((t + 1) * KVB <= skv) {
+      dma_tile_slim(kh + (int64_t)t * kstep, vh + (int64_t)t * vstep, ko[0], ko[1], vo[0], vo[1], l0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        int64_t r = (int64_t)t * KVB + dkey[j];
+        r = r < skv ? r : skv - 1;
+        dma16(kh + r * p.ldk + kcol[j], l0 + j * 1024);
+        dma16(vh + r * p.ldv + vcol[j], l0 + TILE_BYTES + j * 1024);
+      }
+    }
+  };
+#define S_END_SLOT(N_)                                              \
+  do {                                                              \
+    asm volatile("s_waitcnt vmcnt(" #N_ ") lgkmcnt(0)" ::: "memory"); \
+    __builtin_amdgcn_s_barrier();                                   \
+    asm volatile("" ::: "memory");                                  \
+    __builtin_amdgcn_sched_barrier(0);                              \
+  } while (0)
+  // end of a slot of the tail: tile U_ was requested in this slot if it exists
+#define S_END_SLOT_TAIL(U_)          \
+  do {                               \
+    if ((U_) < nt) S_END_SLOT(4);    \
+    else S_END_SLOT(0);              \
+  } while (0)
+
+  attc::Tile16Addr la16;
+  attc::tile16_lean_addr(lds_base, lane, la16);
+  attc::tile16_lean_lim<UNIT>(s16, p_lim, la16);
+  int la_step = 2 * STAGE_BYTES;
+  f32x4 st[4][2];
+
+  if (pp.ptrace && tid == 0) pp.ptrace[blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  dma_tile(0);
+  if (nt > 1) dma_tile(1);
+  S_END_SLOT(0);
+  // ONE program for both groups: every wave runs QK(t) SV(t) for t = 0 .. nt - 1; A ends its slot (and begins the next: the request)
+  // behind SV(t), B behind QK(t).  is_b is wave-uniform: the branches round the barriers are scalar.
+  const bool is_b = SWAP ? wave < NW / 2 : wave >= NW / 2;
+  if (is_b && nt > 2) dma_tile(2);                        // B's slot 0 is QK(0) alone
+  // steady pair of tiles t, t + 1 (t even): tiles t .. t + 4 are full.  A requests tiles t + 2 and t + 3 in front of QK(t) and
+  // QK(t + 1), B tiles t + 3 and t + 4 in front of SV(t) and SV(t + 1): kt_d / vt_d point at the first of the two, d0 / d1 are the
+  // two ring destinations - stages {2, 3} <-> {0, 1} for A, {3, 0} <-> {1, 2} for B, each alternating between its two values
+  const int lead = is_b ? 3 : 2;
+  const bf16_t* kt_d = kh + lead * kstep;
+  const bf16_t* vt_d = vh + lead * vstep;
+  unsigned d0 = l_w + (unsigned)(lead * STAGE_BYTES);
+  unsigned d1 = l_w + (unsigned)(((lead + 1) & (NST - 1)) * STAGE_BYTES);
+  const unsigned d0_sum = 2 * d0 - 2 * STAGE_BYTES, d1_sum = 2 * l_w + (is_b ? 2 : 4) * STAGE_BYTES;
+  const int nfull = skv >> 6;        // full tiles
+  int t = 0;
+  for (; t <= nfull - 5; t += 2) {
+    if (!is_b) dma_tile_slim(kt_d, vt_d, ko[0], ko[1], vo[0], vo[1], d0);
+    attc::tile16_qk<UNIT, 0>(s16, la16, st);
+    if (is_b) {
+      S_END_SLOT(4);
+      dma_tile_slim(kt_d, vt_d, ko[0], ko[1], vo[0], vo[1], d0);
+    }
+    attc::tile16_sv<UNIT, PRIO, 0>(p, p_lim, 0, KVB, lane, s16, la16, st);        // a full tile: no tail mask
+    if (!is_b) {
+      S_END_SLOT(4);
+      dma_tile_slim(kt_d + kstep, vt_d + vstep, ko[0], ko[1], vo[0], vo[1], d1);
+    }
+    attc::tile16_qk<UNIT, 1>(s16, la16, st);
+    if (is_b) {
+      S_END_SLOT(4);
+      dma_tile_slim(kt_d + kstep, vt_d + vstep, ko[0], ko[1], vo[0], vo[1], d1);
+    }
+    attc::tile16_sv<UNIT, PRIO, 1>(p, p_lim, 0, KVB, lane, s16, la16, st);
+    attc::tile16_lean_advance(la16, la_step);
+    la_step = -la_step;
+    kt_d += 2 * kstep;
+    vt_d += 2 * vstep;
+    d0 = d0_sum - d0;
+    d1 = d1_sum - d1;
+    if (!is_b) S_END_SLOT(4);
+  }
+  // the last slots (ragged tile, odd count, drain), t even.  B's SV(nt - 1) stands behind the last barrier
+  for (; t < nt; t += 2) {
+    if (!is_b && t + 2 < nt) dma_tile(t + 2);
+    attc::tile16_qk<UNIT, 0>(s16, la16, st);
+    if (is_b) {
+      S_END_SLOT_TAIL(t + 2);
+      if (t + 3 < nt) dma_tile(t + 3);
+    }
+    attc::tile16_sv<UNIT, PRIO, 0>(p, p_lim, (int64_t)t * KVB, skv, lane, s16, la16, st);
+    if (!is_b) S_END_SLOT_TAIL(t + 2);
+    if (t + 1 >= nt) break;
+    if (!is_b && t + 3 < nt) dma_tile(t + 3);
+    attc::tile16_qk<UNIT, 1>(s16, la16, st);
+    if (is_b) {
+      S_END_SLOT_TAIL(t + 3);
+      if (t + 4 < nt) dma_tile(t + 4);
+    }
+    attc::tile16_sv<UNIT, PRIO, 1>(p, p_lim, (int64_t)(t + 1) * KVB, skv, lane, s16, la16, st);
+    attc::tile16_lean_advance(la16, la_step);
+    la_step = -la_step;
+    if (!is_b) S_END_SLOT_TAIL(t + 3);
+  }
+#undef S_END_SLOT
+#undef S_END_SLOT_TAIL
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  {
+    int64_t qr[2];
+    int t16 = lane & 15;
+    asm volatile("" : "+v"(t16));      // recompute the rows here: carried from the prologue they cost four VGPRs through the whole loop
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) qr[qb] = q0 + qb * 16 + t16;
+    attc::store_result(p, qr, head, lane >> 4, s16.ot, s16.m_run, s16.l_run);
+  }
+  if (p.trace && tid == 0 && (int)blockIdx.x < p.trace_cap) {
+    unsigned hwid, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    unsigned long long* tr = p.trace + (size_t)blockIdx.x * 4;
+    tr[0] = t_start; tr[1] = __builtin_amdgcn_s_memrealtime(); tr[2] = hwid; tr[3] = xcc;
+  }
+}
+
+template <bool UNIT, bool PRIO, bool SWAP>
+int launch_stagger(const Params& pp, hipStream_t st) {
+  static icv_dev_flags attr_set = {};
+  if (int rc = icv_ensure_dynamic_lds((const void*)attn7ps_kernel<UNIT, PRIO, SWAP>, NST * STAGE_BYTES, &attr_set, "attn7ps")) return rc;
+  const int64_t nwg = (int64_t)pp.a.heads * pp.a.nqb;
+  hipLaunchKernelGGL((attn7ps_kernel<UNIT, PRIO, SWAP>), dim3((unsigned)nwg), dim3(NW * 64), NST * STAGE_BYTES, st, pp);
+  return icv_check_launch("icv_attention_fwd (staggered)");
+}
+
 template <bool UNIT, bool FW, int MF, bool SLIM = false, bool LEAN = false>
 int launch_mf(const Params& pp, hipStream_t st) {
   static icv_dev_flags attr_set = {};
@@ -566,7 +775,16 @@ int launch(const Params& pp, hipStream_t st) {
     const int slim = icv_attn7p_slim();             // form of the key loop around the lean body (option "attn7p_slim")
     if (slim < 0) return 1;
     // dma_tile_slim takes a lane offset 1 KiB short of a row >= 4: rows of 256 B or more, which is every layout but a degenerate one
-    if (slim && pp.a.ldk >= D && pp.a.ldv >= D) return launch_mf<UNIT, FW, 16, true, true>(pp, st);
+    if (slim && pp.a.ldk >= D && pp.a.ldv >= D) {
+      const int stagger = icv_attn7p_stagger();     // one piece that is there: the staggered kernel (option "attn7p_stagger")
+      const int prio = icv_attn7p_stagger_setprio(), swap = icv_attn7p_stagger_swap();
+      if (stagger < 0 || prio < 0 || swap < 0) return 1;
+      if (stagger && pp.n_pieces == 1 && pp.piece[0].flag < 0) {
+        if (swap) return prio ? launch_stagger<UNIT, true, true>(pp, st) : launch_stagger<UNIT, false, true>(pp, st);
+        return prio ? launch_stagger<UNIT, true, false>(pp, st) : launch_stagger<UNIT, false, false>(pp, st);
+      }
+      return launch_mf<UNIT, FW, 16, true, true>(pp, st);
+    }
   }
   return launch_mf<UNIT, FW, 16, false, true>(pp, st);
 }

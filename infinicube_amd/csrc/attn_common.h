@@ -11,6 +11,9 @@ unsigned long long* icv_attention_trace_buffer(int* capacity);   // attention.hi
 int icv_attn_mfma(bool short_kv);                                // attention.hip: MFMA shape of attn7 / attn7p (16 or 32; -1 = error set)
 int icv_attn_tile16_lean(bool short_kv);                         // attention.hip: body of the MF = 16 tile (1 = lean, 0 = the first one)
 int icv_attn7p_slim();                                           // attention.hip: attn7p's key loop around the lean body (1 = slim, 0 = the one loop)
+int icv_attn7p_stagger();                                        // attention.hip: attn7p's staggered kernel for one piece that is there (1 / 0; -1 = error set)
+int icv_attn7p_stagger_setprio();                                // attention.hip: s_setprio over softmax + PV in the staggered kernel (1 / 0; -1 = error set)
+int icv_attn7p_stagger_swap();                                   // attention.hip: which half of the work-group opens a slot with the softmax (1 / 0; -1 = error set)
 
 namespace attc {
 
@@ -473,6 +476,148 @@ __device__ __forceinline__ void tile16(const Params& p, const float p_lim, const
   s.l_run[0] += psum[0];
   if (LEAN) s.l_run[1] = t16_add_opaque(s.l_run[1], psum[1], one);
   else s.l_run[1] += psum[1];
+}
+
+// The lean body of tile16<UNIT, false, true, SETPRIO, true, STG> cut in two, for a key loop that may put a barrier between the halves
+// (attn7p.hip's staggered kernel): tile16_qk is the K fragment reads and the 32 QK^T MFMAs into st, tile16_sv everything behind them -
+// tail mask, both 32-key halves of softmax with lazy max and re-base, the V tr-reads and the 32 PV MFMAs.  The lean body's code in the
+// lean body's order, statement for statement: tile16_qk + tile16_sv on one tile IS tile16's lean body, so outputs and carried state are
+// bit-identical whichever loop runs them (tests/test_attn_stagger_gpu.py).  st (32 VGPRs) is the caller's, so that it can outlive a
+// barrier.  Change tile16's lean body and these two together.
+template <bool UNIT, int STG>
+__device__ __forceinline__ void tile16_qk(const Tile16& s, const Tile16Addr& la, f32x4 (&st)[4][2]) {
+  static_assert(STG == 0 || STG == 1, "STG: the tile's place in a step of two stages");
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#define T16_KLOAD(DST_, KB_, KS_) DST_ = *(const lds_bf16x8*)(la.k[KS_] + (unsigned)(STG * 32768 + (KB_) * 4096))
+#define T16_QK(KB_, KS_, KF_)                                                                                       \
+  _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) st[KB_][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(           \
+      KF_, s.qf[qb][KS_], (KS_) == 0 ? (UNIT ? s.cinit[qb] : zero4) : st[KB_][qb], 0, 0, 0)
+  constexpr int KD = 3;
+  bf16x8 kf[16];
+#pragma unroll
+  for (int i = 0; i < KD; ++i) T16_KLOAD(kf[i], i & 3, i >> 2);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if (i + KD < 16) T16_KLOAD(kf[i + KD], (i + KD) & 3, (i + KD) >> 2);
+    T16_QK(i & 3, i >> 2, kf[i]);
+  }
+  __builtin_amdgcn_sched_group_barrier(0x100, KD, 0);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if (i + KD < 16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+  }
+#undef T16_KLOAD
+#undef T16_QK
+}
+
+template <bool UNIT, bool SETPRIO, int STG>
+__device__ __forceinline__ void tile16_sv(const Params& p, const float p_lim, const int64_t key0, const int64_t skv, const int lane, Tile16& s,
+                                          Tile16Addr& la, f32x4 (&st)[4][2]) {
+  static_assert(STG == 0 || STG == 1, "STG: the tile's place in a step of two stages");
+  const int g = lane >> 4;
+  if (key0 + 64 > skv) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t key = key0 + kb * 16 + 4 * g + r;
+        if (key >= skv) { st[kb][0][r] = NEG_BIG; st[kb][1][r] = NEG_BIG; }
+      }
+  }
+  float one = 1.0f;                          // see t16_add_opaque
+  asm("" : "+s"(one));
+  float mb[2] = {-s.m_run[0] * p.sc, -s.m_run[1] * p.sc};
+  float psum[2] = {0.f, 0.f};
+  if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {          // a 32-key half = key blocks 2 kk and 2 kk + 1 = one k-step of the PV MFMAs
+    bf16x8 pf[2];
+    float ps[2];
+#define T16_EXP()                                                                                                   \
+  _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) {                                                                \
+    ps[qb] = 0.f;                                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                 \
+      const float sv = st[2 * kk + (j >> 2)][qb][j & 3];                                                            \
+      const float pv = UNIT ? __builtin_amdgcn_exp2f(sv) : __builtin_amdgcn_exp2f(fmaf(sv, p.sc, mb[qb]));          \
+      if (j == 0) ps[qb] = pv; /* 0 + pv, exactly */                                                                \
+      else if (qb == 1) ps[qb] = t16_add_opaque(ps[qb], pv, one);                                                   \
+      else ps[qb] += pv;                                                                                            \
+      pf[qb][j] = (__bf16)pv;                                                                                       \
+    }                                                                                                               \
+  }
+    T16_EXP();
+    // lazy max (attn2.hip): the lane's partial row sum bounds every P it holds
+    if (__any(UNIT ? !(ps[0] <= la.lim[0]) || !(ps[1] <= la.lim[1]) : !(ps[0] <= p_lim) || !(ps[1] <= p_lim))) {
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) {
+        float mloc = st[2 * kk][qb][0];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) mloc = fmaxf(mloc, st[2 * kk + (j >> 2)][qb][j & 3]);
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+        if (UNIT) mloc += s.m_base[qb];                      // st = s - m_base
+        const float m_new = fmaxf(s.m_run[qb], mloc);
+        const float alpha = __builtin_amdgcn_exp2f((s.m_run[qb] - m_new) * p.sc);
+        s.m_run[qb] = m_new;
+        // an empty m_run at the top of the tile forces the re-base in BOTH halves, so the second half's sees the final one
+        if (UNIT && kk == 1) la.lim[qb] = m_new < -1.0e29f ? -1.0f : p_lim;
+        s.l_run[qb] = (s.l_run[qb] + psum[qb]) * alpha;
+        psum[qb] = 0.f;
+#pragma unroll
+        for (int db = 0; db < 8; ++db)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s.ot[db][qb][r] *= alpha;
+        mb[qb] = -m_new * p.sc;
+        if (UNIT) {                                          // re-base this and the later half of the tile, and cinit
+          const float dm = m_new - s.m_base[qb];
+          s.m_base[qb] = m_new;
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb)
+            if (kb >= 2 * kk) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) st[kb][qb][r] -= dm;
+            }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s.cinit[qb][r] = -m_new;
+        }
+      }
+      T16_EXP();
+    }
+#undef T16_EXP
+    psum[0] = kk == 0 ? ps[0] : psum[0] + ps[0];             // ps >= +0, so 0 + ps = ps exactly
+    psum[1] = kk == 0 ? ps[1] : t16_add_opaque(psum[1], ps[1], one);
+    // the V fragments VD d-blocks ahead of their MFMAs, pinned the same way (the next half's exp / convert work floats between them)
+    constexpr int VD = 2;
+    bf16x4 va[8], vb[8];
+#define T16_VREAD(DB_)                                                                                  \
+  {                                                                                                     \
+    const unsigned va_a = la.v[DB_] + (unsigned)(STG * 32768 + kk * 8192);                              \
+    va[DB_] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va_a)));  \
+    vb[DB_] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va_a + 4096u))); \
+  }
+#pragma unroll
+    for (int db = 0; db < VD; ++db) T16_VREAD(db);
+#pragma unroll
+    for (int db = 0; db < 8; ++db) {
+      if (db + VD < 8) T16_VREAD(db + VD);
+      bf16x8 vf;
+      vf[0] = va[db][0]; vf[1] = va[db][1]; vf[2] = va[db][2]; vf[3] = va[db][3];
+      vf[4] = vb[db][0]; vf[5] = vb[db][1]; vf[6] = vb[db][2]; vf[7] = vb[db][3];
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) s.ot[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb], s.ot[db][qb], 0, 0, 0);
+    }
+#undef T16_VREAD
+    __builtin_amdgcn_sched_group_barrier(0x100, 2 * VD, 0);
+#pragma unroll
+    for (int db = 0; db < 8; ++db) {
+      if (db + VD < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    }
+  }
+  if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+  s.l_run[0] += psum[0];
+  s.l_run[1] = t16_add_opaque(s.l_run[1], psum[1], one);
 }
 
 }  // namespace attc
