@@ -43,7 +43,8 @@ extern "C" {
  *    icv_latent_keep_mask_u8 and icv_pin_known_f32 (input_mask: the known cells of a clip pinned after every step);
  *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output);
  *    icv_enhance_scores_bf16 and icv_enhance_apply_bf16 (Enhance-A-Video: the cross-frame attention boost of a self-attention output);
- *    icv_attention_fwd_radial (radial self-attention in one launch: every frame in reach, bands that halve with the distance). */
+ *    icv_attention_fwd_radial (radial self-attention in one launch: every frame in reach, bands that halve with the distance);
+ *    icv_l1_change_f64 and icv_easycache_predict_f32 (EasyCache: the sums of the skip rule and a skipped step's head outputs). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -674,6 +675,33 @@ int icv_enhance_scores_bf16(const void* q, int64_t ldq, const void* k, int64_t l
                             float weight, float* workspace, float* score_out, void* stream);
 int icv_enhance_apply_bf16(void* att, int64_t ld, int64_t rows, int64_t d, const float* workspace, int64_t T, int64_t P, int64_t heads,
                            float weight, float* score_out, void* stream);
+
+/* ---- EasyCache runtime-adaptive step skipping: easy_cache_thresh -----------------------------------------------
+ * icv_l1_change_f64: a (read only), b: f32 [rows, cols] with row strides lda, ldb >= cols (elements).  Over all rows * cols
+ * elements, every term formed in fp64 from the f32 values:
+ *     out2[0] = sum |a - b|        out2[1] = sum |a|
+ * With update_b != 0 also b <- a in the same pass: each element of a is read once and each thread overwrites only the elements of
+ * b it read.  Columns >= cols of a row and rows >= rows are not touched, in either operand.  Two launches on ``stream``: the first
+ * leaves one pair of partial sums per block in ``workspace`` (ICV_L1_CHANGE_WORKSPACE_DOUBLES doubles, 8-byte aligned, device
+ * memory), the second adds them in one block in one fixed order and stores the two doubles of ``out2`` (8-byte aligned, device
+ * memory, outside the workspace).  No atomics and no host read; the grid and the assignment of elements to threads depend on
+ * (rows, cols) only, so the same inputs give the same bits, whatever the pointers' alignment and the strides (16-byte accesses
+ * are used where a, b, lda and ldb allow them; any 4-byte-aligned pointers and any strides work).  a and b must not overlap.
+ * Every argument check runs on the host before the first launch.
+ *
+ * icv_easycache_predict_f32: a skipped step's head outputs from the last computed step's.  x, x_last: f32 [C, T, H8, W8] latents;
+ * h*_last, h*: f32 [n_tok, 4*C] head outputs (ldh).  For local token r in [0, n_tok), token tok0 + r = (f, hp, wp), and column
+ * (y*2+z)*C + c - icv_unpatchify_cfg_euler's index map, read in the other direction:
+ *     h[r, col] = h_last[r, col] + (x[c, f, 2hp+y, 2wp+z] - x_last[c, f, 2hp+y, 2wp+z])
+ * in plain f32, the subtraction first, for hc and - unless hu_last and hu are both NULL - for hu, in ONE launch.  Rows outside the
+ * range and columns >= 4*C of a row are not touched; the inputs are read only and the outputs must be buffers of their own.
+ * H8, W8 even, x and x_last 8-byte aligned, the head pointers 4-byte aligned (16-byte accesses where C, ldh and they allow).
+ * Every argument check runs on the host before the launch. */
+#define ICV_L1_CHANGE_WORKSPACE_DOUBLES 512
+int icv_l1_change_f64(const float* a, int64_t lda, float* b, int64_t ldb, int64_t rows, int64_t cols, int update_b,
+                      double* workspace, double* out2, void* stream);
+int icv_easycache_predict_f32(const float* x, const float* x_last, const float* hc_last, const float* hu_last, float* hc, float* hu,
+                              int64_t ldh, int64_t C, int64_t T, int64_t H8, int64_t W8, int64_t tok0, int64_t n_tok, void* stream);
 
 #ifdef __cplusplus
 }

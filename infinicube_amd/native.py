@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("ICV_LIB_PATH") or os.path.join(_HERE, "csrc", "libicv
 EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, EPI_F32 = 0, 1, 2, 3
 CFG_ZERO_WORKSPACE_DOUBLES = 512      # ICV_CFG_ZERO_WORKSPACE_DOUBLES (icv_cfg_zero_scale_f32's partial sums)
 ENHANCE_WORKSPACE_FLOATS = 16384      # ICV_ENHANCE_WORKSPACE_FLOATS (icv_enhance_scores_bf16's partial sums, one per position)
+L1_CHANGE_WORKSPACE_DOUBLES = 512     # ICV_L1_CHANGE_WORKSPACE_DOUBLES (icv_l1_change_f64's partial sums)
 ACT_NONE, ACT_SILU = 0, 1
 
 # name -> (restype, argtypes); must list EVERY symbol include/icvideo.h declares
@@ -123,6 +124,8 @@ SIGNATURES.update({
     "icv_nag_combine_bf16": (c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _F, _P]),
     "icv_enhance_scores_bf16": (c_int, [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "icv_enhance_apply_bf16": (c_int, [_P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _P]),
+    "icv_l1_change_f64": (c_int, [_P, _I, _P, _I, _I, _I, c_int, _P, _P, _P]),
+    "icv_easycache_predict_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
 })
 
 class KVPiece(ctypes.Structure):

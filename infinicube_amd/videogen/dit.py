@@ -41,7 +41,7 @@ from typing import Dict, Optional
 
 import torch
 
-from ..native import CFG_ZERO_WORKSPACE_DOUBLES
+from ..native import CFG_ZERO_WORKSPACE_DOUBLES, L1_CHANGE_WORKSPACE_DOUBLES
 from . import options
 from .config import TokenGrid, WanDiTConfig
 from .ops import BF16, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32, F32, FP8, RopeTable
@@ -366,6 +366,9 @@ class WanDiT:
         # per-position partial sums of this workspace (f32 [P]) and the factors E (f32 [2, L]), both allocated on first use;
         # enhance_scores: E per layer per branch of the last enhanced call's last computed forward (host, read back once per call)
         self._enhance, self._enhance_slot, self._enhance_ws, self._enhance_E, self.enhance_scores = None, 0, None, None, None
+        # EasyCache (easycache.py): x_prev, x_last (f32, the latent's shape), h_last (f32, head_out's shape), the fp64 partial-sum
+        # workspace and the 8 doubles one step's decision reads - allocated on first use
+        self._easy_state = None
         # sliding temporal windows (denoise(sliding_window=)): where this engine's window starts in the clip's latent, in tokens
         # (None = no window: the latent is this engine's own grid), the engines of other window lengths, the second latent
         self._lat_tok0, self._win_engines, self._win_next = None, {}, None
@@ -1069,6 +1072,7 @@ class WanDiT:
         t._guidance_state, t.guidance_scales = None, None
         t._nag, t._nag_buf = None, None
         t._enhance, t._enhance_slot, t._enhance_ws, t._enhance_E, t.enhance_scores = None, 0, None, None, None
+        t._easy_state = None
         return t
 
     def _pair_engine(self):
@@ -1141,6 +1145,15 @@ class WanDiT:
             self._guidance_state = (self.ops.alloc((CFG_ZERO_WORKSPACE_DOUBLES,), torch.float64), self.ops.alloc((n_steps,), F32))
         return self._guidance_state
 
+    def _easy_buffers(self, latent: torch.Tensor):
+        """(x_prev, x_last, h_last, workspace f64 [ICV_L1_CHANGE_WORKSPACE_DOUBLES], sums f64 [8]) of EasyCache: the four state buffers
+        (two latent-shaped, the two head outputs of the last computed step) and the reduction's memory, once per prepared grid."""
+        if self._easy_state is None or self._easy_state[0].shape != latent.shape or self._easy_state[2].shape != self.head_out.shape:
+            a = self.ops.alloc
+            self._easy_state = (a(tuple(latent.shape), F32), a(tuple(latent.shape), F32), a(tuple(self.head_out.shape), F32),
+                                a((L1_CHANGE_WORKSPACE_DOUBLES,), torch.float64), a((8,), torch.float64))
+        return self._easy_state
+
     @staticmethod
     def _nag_rows(t):
         """The second attention-output buffer of workspace ``t`` (the negative text's softmax), bf16 like ``t.att``: first use only."""
@@ -1203,7 +1216,7 @@ class WanDiT:
                 buf_tokens: Optional[torch.Tensor], scheduler: FlowMatchScheduler,
                 cfg_scale: float = 5.0, steps: Optional[range] = None, on_step=None,
                 branch_exchange=None, round_bf16: bool = False, tea_cache=None, sliding_window=None, solver=None,
-                guidance=None, known=None, nag=None, enhance=None) -> torch.Tensor:
+                guidance=None, known=None, nag=None, enhance=None, easy_cache=None) -> torch.Tensor:
         """The hot loop: per step 2 DiT forwards (cond, uncond) + fused unpatchify/CFG/Euler.
         ``latent`` f32 [C,T,H8,W8] is updated IN PLACE for this rank's tokens.
         ``branch_exchange`` (seqpar.BranchExchange, cfg+sp layout): this rank runs ONE forward per step — the
@@ -1239,7 +1252,16 @@ class WanDiT:
         icv_enhance_apply_bf16 scales its attention output by E = max(1, (T + weight) * mean) in place; E stays on the device, in
         an f32 [2, L] buffer that is read back once after the loop (``self.enhance_scores``: E per layer per branch of the last
         computed forward).  The per-op driver runs; a captured graph is keyed on the weight.  None: today's launches, allocations
-        and bits."""
+        and bits.
+        ``easy_cache`` (easycache.EasyCachePlan, EasyCache): every executed step measures sum|x - x_prev| and sum|x - x_last| of its
+        input latent (icv_l1_change_f64, on the stream of the step's update launch), reads at most 8 doubles back - the ONE blocking
+        host read of the step, the loop's only data-dependent control - and applies the rule of easycache.py in float64.  A computed
+        step is today's computed step in whatever mode this engine is set up for, followed by the sums of its conditional head output
+        against the last computed one's (read with the NEXT step's sums) and the copies that keep x_last / h_last.  A skipped step runs
+        no forward: one icv_easycache_predict_f32 leaves head = h_last + P(x - x_last) for both branches where the update launch
+        expects them; the CFG-Zero* scale, the Euler / multistep update and the pin run unchanged.  The plan's record lists are filled
+        as the loop runs.  Not with TeaCache, more than one sliding window or more than one rank.  None: today's launches,
+        allocations and bits, no host read."""
         ops, plan = self.ops, self.plan
         self.guidance_scales = None
         self._nag, self._enhance, self._enhance_slot, self.enhance_scores = None, None, 0, None
@@ -1274,6 +1296,15 @@ class WanDiT:
             from . import enhance as enhance_mod
             enhance_mod.validate(enhance.weight)
             enhance_mod.check_frames(self.grid.T, "denoise: Enhance-A-Video (enhance=)")
+        if easy_cache is not None:
+            if tea_cache is not None:
+                raise ValueError("denoise: EasyCache (easy_cache=) cannot be combined with TeaCache (tea_cache=) in the same call yet")
+            if parallel:
+                raise ValueError(f"denoise: EasyCache (easy_cache=) cannot be combined with {parallel} yet")
+            if windows:
+                raise ValueError("denoise: EasyCache (easy_cache=) cannot be combined with more than one sliding temporal window yet")
+            if ctx_cond is None:
+                raise ValueError("denoise: EasyCache (easy_cache=) measures the conditional head output: pass ctx_cond")
         if known is not None:
             if parallel:
                 raise ValueError(f"denoise: known cells (input_mask) cannot be combined with {parallel} yet")
@@ -1290,7 +1321,7 @@ class WanDiT:
             self._enhance_E.fill_(float("nan"))
         try:
             out = self._denoise_loop(latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange,
-                                     round_bf16, tea_cache, solver, guidance, known)
+                                     round_bf16, tea_cache, solver, guidance, known, easy_cache)
             if enhance is not None and self._enhance_E is not None:
                 self.enhance_scores = self._enhance_read(2 if ctx_cond is not None and ctx_uncond is not None and cfg_scale != 1.0 else 1)
             return out
@@ -1307,7 +1338,7 @@ class WanDiT:
         return None if vals.numel() == 0 or bool(torch.isnan(vals).any()) else vals.tolist()
 
     def _denoise_loop(self, latent, ctx_cond, ctx_uncond, buf_tokens, scheduler, cfg_scale, steps, on_step, branch_exchange, round_bf16,
-                      tea_cache, solver, guidance, known):
+                      tea_cache, solver, guidance, known, easy_cache=None):
         """denoise() behind its checks: the loop over one window."""
         ops, plan = self.ops, self.plan
         res = self._tc_residuals() if tea_cache is not None else None
@@ -1324,6 +1355,9 @@ class WanDiT:
         gd_work = gd_out = None                                        # allocated at the first scaled step, after everything else
         sigma_after = lambda i: scheduler.sigmas[i + 1] if i + 1 < len(scheduler.sigmas) else 0.0      # noqa: E731
         repin = False                                                  # zero-init steps were skipped: the kept cells sit at the start sigma
+        ec = easy_cache.begin() if easy_cache is not None else None   # EasyCache: the rule's state of this call (easycache.Rule)
+        ec_pending = False                                             # a computed step's output sums are on the device, not read yet
+        last_step = len(scheduler.sigmas) - 1
         for i in (steps if steps is not None else range(len(scheduler.sigmas))):
             if guidance is not None:
                 if guidance.skips(i):                                  # zero-init: the velocity is zero, so nothing runs
@@ -1337,7 +1371,30 @@ class WanDiT:
                 ops.pin_known(latent, known.x0, known.noise, known.keep, scheduler.sigmas[i], round_bf16=round_bf16)
                 repin = False
             ts = scheduler.timesteps[i]
-            if res is not None and tea_cache.skip(i):
+            ec_skip = False
+            if ec is not None:
+                # the sums of this step's input (and, behind them in the same 8 doubles, the last computed step's output sums), ONE read
+                x_prev, x_last, h_last, ec_work, ec_sums = self._easy_buffers(latent)
+                x_row = latent.view(1, -1)
+                ops.l1_change(x_row, x_prev.view(1, -1), ec_work, ec_sums[0:2], update_b=True)      # sum|x_i - x_prev|; x_prev <- x_i
+                if ec.j is not None:
+                    ops.l1_change(x_row, x_last.view(1, -1), ec_work, ec_sums[2:4])                  # sum|x_i - x_j|
+                got = ops.read_doubles(ec_sums)
+                n_x, n_v = float(latent.numel()), float(plan.n_tok * self.head_out.shape[-1])
+                if ec_pending:
+                    ec.output(got[4] / n_v, got[5] / n_v)
+                    ec_pending = False
+                d_x = got[2] / n_x if ec.j is not None else None
+                ec_skip, k_now, compared = ec.decide(i, i == last_step, got[0] / n_x)
+                easy_cache.k.append(k_now)
+                easy_cache.accumulated.append(compared)
+                (easy_cache.skipped if ec_skip else easy_cache.computed).append(int(i))
+            if ec_skip:
+                # EasyCache: no forward at all; both branches' head outputs from the last computed step's, in one launch
+                two = len(ctxs) == 2
+                ops.easycache_predict(latent, x_last, h_last[0], h_last[1] if two else None, self.head_out[0],
+                                      self.head_out[1] if two else None, plan.tok0, plan.n_tok)
+            elif res is not None and tea_cache.skip(i):
                 # TeaCache: no blocks, so no K|V exchange either (every rank skips the same steps); both branches on this stream
                 for ctx, r, out in zip(ctxs, res, outs):
                     self.forward_tokens(latent, ctx, ts, r, out, num_layers=0)
@@ -1345,6 +1402,15 @@ class WanDiT:
                 for b, patches, x in self._computed_step(latent, ctxs, ts, buf_tokens, outs):
                     if res is not None:
                         self._tc_store(patches, x, res[b])
+            if ec is not None and not ec_skip:
+                # behind the forwards' fences, on the update launch's stream: sum|v_i - v_j|, sum|v_i| and h_last[0] <- v_i in one pass
+                # (read with the next step's sums), then the other two state buffers
+                ops.l1_change(self.head_out[0][:plan.n_tok], h_last[0][:plan.n_tok], ec_work, ec_sums[4:6], update_b=True)
+                if len(ctxs) == 2:
+                    h_last[1].copy_(self.head_out[1])
+                x_last.copy_(latent)
+                ec.computed(i, d_x)
+                ec_pending = True
             if branch_exchange is not None:
                 branch_exchange(self.head_own, self.head_out)           # slot 0 = cond, slot 1 = uncond
             if gd_scale:

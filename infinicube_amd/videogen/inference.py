@@ -165,6 +165,9 @@ class WanVideoGenerator:
             from . import nag          # attributes without an options row: the ranks would never see them
             if nag.validate(*(getattr(self.pipe, n, None) for n in ("nag_scale", "nag_tau", "nag_alpha"))) is not None:
                 raise ValueError("pipe.nag_scale cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
+            from . import easycache
+            if easycache.validate(getattr(self.pipe, "easy_cache_thresh", None), getattr(self.pipe, "easy_cache_warmup_steps", None)) is not None:
+                raise ValueError("pipe.easy_cache_thresh cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
             from . import enhance
             if enhance.validate(getattr(self.pipe, "enhance_weight", None)) is not None:
                 raise ValueError("pipe.enhance_weight cannot be combined with ICV_WORLD > 1 (more than one rank) yet")

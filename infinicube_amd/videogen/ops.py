@@ -494,6 +494,52 @@ class HipOps:
             if score_out.numel() != 1:
                 raise ValueError(f"{who}: score_out must be an f32 tensor of one element")
 
+    # ---- EasyCache step skipping (easycache.py) ---------------------------------------
+    def l1_change(self, a, b, workspace, out2, update_b=False):
+        """out2[0] = sum|a - b|, out2[1] = sum|a| in fp64 over a, b f32 [rows, cols] (row strides allowed; a latent goes in as one
+        row); with ``update_b`` also b <- a in the same pass (icv_l1_change_f64: two launches, fixed summation order, no atomics, no
+        host read).  workspace: f64 [ICV_L1_CHANGE_WORKSPACE_DOUBLES]; out2: f64, two contiguous elements outside the workspace."""
+        _chk(a, F32, "l1_change.a"); _chk(b, F32, "l1_change.b")
+        _chk(workspace, torch.float64, "l1_change.workspace"); _chk(out2, torch.float64, "l1_change.out2")
+        if a.dim() != 2 or tuple(a.shape) != tuple(b.shape) or a.numel() == 0:
+            raise ValueError(f"l1_change: a and b must be [rows, cols] of one non-empty shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        if workspace.numel() < native.L1_CHANGE_WORKSPACE_DOUBLES or not workspace.is_contiguous() or out2.numel() != 2 or not out2.is_contiguous():
+            raise ValueError(f"l1_change: workspace must hold {native.L1_CHANGE_WORKSPACE_DOUBLES} contiguous doubles and out2 two")
+        rows, cols = a.shape
+        lda, ldb = (a.stride(0), b.stride(0)) if rows > 1 else (cols, cols)
+        native.check(self.lib.icv_l1_change_f64(a.data_ptr(), lda, b.data_ptr(), ldb, rows, cols, int(bool(update_b)),
+                                                workspace.data_ptr(), out2.data_ptr(), self._stream()), "icv_l1_change_f64")
+
+    def easycache_predict(self, x, x_last, hc_last, hu_last, hc, hu, tok0, n_tok):
+        """A skipped step's head outputs: for the local tokens, h = h_last + P(x - x_last) with P the head-output layout of a latent
+        (unpatchify_cfg_euler's index map read in the other direction), for hc and - unless hu_last and hu are both None - hu, in ONE
+        launch (icv_easycache_predict_f32).  x, x_last f32 [C, T, H8, W8]; the four head tensors f32 [>= n_tok, >= 4*C], one stride."""
+        _chk(x, F32, "easycache_predict.x"); _chk(x_last, F32, "easycache_predict.x_last")
+        if x.dim() != 4 or tuple(x_last.shape) != tuple(x.shape) or not x.is_contiguous() or not x_last.is_contiguous():
+            raise ValueError(f"easycache_predict: x and x_last must be contiguous [C, T, H8, W8] latents of one shape, got {tuple(x.shape)} and {tuple(x_last.shape)}")
+        if (hu_last is None) != (hu is None):
+            raise ValueError("easycache_predict: hu_last and hu must be given together")
+        C = x.shape[0]
+        heads = [t for t in (hc_last, hu_last, hc, hu) if t is not None]
+        for t in heads:
+            _chk(t, F32, "easycache_predict.head")
+            if t.dim() != 2 or t.shape[0] < n_tok or t.shape[1] < 4 * C or t.stride(0) != hc.stride(0):
+                raise ValueError("easycache_predict: head outputs have fewer rows than n_tok or fewer than 4*C columns (or differ in row stride)")
+        if len({t.data_ptr() for t in heads}) != len(heads):
+            raise ValueError("easycache_predict: the head outputs must be buffers of their own")
+        C, T, H8, W8 = x.shape
+        native.check(self.lib.icv_easycache_predict_f32(x.data_ptr(), x_last.data_ptr(), hc_last.data_ptr(), native.ptr(hu_last), hc.data_ptr(),
+                                                        native.ptr(hu), hc.stride(0), C, T, H8, W8, tok0, n_tok, self._stream()),
+                     "icv_easycache_predict_f32")
+
+    def read_doubles(self, t):
+        """The values of a small f64 device tensor (at most 8 doubles = 64 bytes) as Python floats: ONE blocking read on the current
+        stream - EasyCache's per-step sums, the only data-dependent loop control of the denoising loop."""
+        _chk(t, torch.float64, "read_doubles.t")
+        if t.numel() > 8 or not t.is_contiguous():
+            raise ValueError(f"read_doubles: at most 8 contiguous doubles, got {tuple(t.shape)}")
+        return t.cpu().tolist()
+
     def unpatchify_cfg_euler_window(self, latent_next, hc, hu, cfg_scale, dsigma, frame_coef, frame0, tok0, n_tok, round_bf16=False):
         """Sliding temporal windows (sliding_window.py): latent_next[:, frame0 + f] += frame_coef[f] * (CFG(hc, hu) * dsigma) for the
         window-local tokens [tok0, tok0 + n_tok); hc / hu f32 [n_tok, 4*C], frame_coef f32 [frames of the window] on the device."""

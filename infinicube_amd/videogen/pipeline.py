@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import attn_window, enhance, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
+from . import attn_window, easycache, enhance, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -278,6 +278,11 @@ class WanVideoPipeline:
         # self-attention output is scaled by its cross-frame share.  enhance_record: {"weight", "frames", "scores"} of the last call
         self.enhance_weight = None
         self.enhance_record = None
+        # EasyCache (easycache.py): attributes behind the keywords of the same names, no environment route; a step whose
+        # predicted output change stays under the threshold runs no DiT forward.  easy_cache_record: {"thresh", "warmup_steps",
+        # "computed", "skipped", "k", "accumulated"} of the last call
+        self.easy_cache_thresh = self.easy_cache_warmup_steps = None
+        self.easy_cache_record = None
         # Radial attention (attn_window.py): the attribute behind the keyword of the same name, no environment route;
         # True turns attention_window_frames / attention_sink_frames into the dense run and the anchor of a radial mask.  The call's
         # attention_window_record then carries "radial": True, "key_fraction" in rows and "max_pieces"
@@ -470,7 +475,8 @@ class WanVideoPipeline:
                  sample_solver: Optional[str] = None, cfg_zero_star: Optional[bool] = None,
                  cfg_zero_init_steps: Optional[int] = None, input_mask=None, nag_scale: Optional[float] = None,
                  nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, enhance_weight: Optional[float] = None,
-                 attention_radial: Optional[bool] = None, **unused):
+                 attention_radial: Optional[bool] = None, easy_cache_thresh: Optional[float] = None,
+                 easy_cache_warmup_steps: Optional[int] = None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -484,6 +490,7 @@ class WanVideoPipeline:
         self.inpaint_record = None                   # input_mask is a keyword without an environment route: not an options row
         self.nag_record = None                       # ... and so are nag_scale / nag_tau / nag_alpha (keyword, else attribute)
         self.enhance_record = None                   # ... and enhance_weight
+        self.easy_cache_record = None                # ... and easy_cache_thresh / easy_cache_warmup_steps
         # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
         # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
         # same bits), the attention window when it does not cover the clip (the same).
@@ -506,6 +513,8 @@ class WanVideoPipeline:
         nag_on = nag.validate(*(getattr(self, n) if kw is None else kw for n, kw in
                                 (("nag_scale", nag_scale), ("nag_tau", nag_tau), ("nag_alpha", nag_alpha))))      # (scale, tau, alpha) | None
         enhance_on = enhance.validate(self.enhance_weight if enhance_weight is None else enhance_weight)      # weight | None
+        easy_on = easycache.validate(self.easy_cache_thresh if easy_cache_thresh is None else easy_cache_thresh,
+                                     self.easy_cache_warmup_steps if easy_cache_warmup_steps is None else easy_cache_warmup_steps)
         world, rank = 1, 0
         try:
             import torch.distributed as dist
@@ -531,6 +540,8 @@ class WanVideoPipeline:
             nag.check_call(cfg_scale, world, windows)
         if enhance_on is not None:
             enhance.check_call(world, windows, grid.T)
+        if easy_on is not None:
+            easycache.check_call(world, windows, opt.tea_cache_l1_thresh is not None)
         engine = self._get_engine()
         ops = engine.ops
         tc_thresh, tc_id = teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, engine.cfg,
@@ -585,6 +596,7 @@ class WanVideoPipeline:
             nag_plan = nag.NagPlan(engine.encode_context(self.text_encoder.encode(negative_prompt), clip_fea), *nag_on)
             self.nag_record = nag_plan.record()
         enhance_plan = enhance.EnhancePlan(enhance_on) if enhance_on is not None else None
+        easy_plan = easycache.EasyCachePlan(*easy_on) if easy_on is not None else None
         # noise: CPU generator, fp32 (rand_device='cpu' upstream) -> identical across devices/ranks
         g = torch.Generator(device="cpu")
         if seed is None:
@@ -677,7 +689,10 @@ class WanVideoPipeline:
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
                        round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan,
                        **(dict(known=known) if known is not None else {}), **(dict(nag=nag_plan) if nag_plan is not None else {}),
-                       **(dict(enhance=enhance_plan) if enhance_plan is not None else {}))
+                       **(dict(enhance=enhance_plan) if enhance_plan is not None else {}),
+                       **(dict(easy_cache=easy_plan) if easy_plan is not None else {}))
+        if easy_plan is not None:
+            self.easy_cache_record = easy_plan.record()
         if enhance_plan is not None:
             self.enhance_record = enhance_plan.record(engine.grid.T, engine.enhance_scores)
         if gd_plan is not None:
