@@ -44,7 +44,8 @@ extern "C" {
  *    icv_nag_combine_bf16 (Normalized Attention Guidance: the negative prompt applied to the text cross-attention output);
  *    icv_enhance_scores_bf16 and icv_enhance_apply_bf16 (Enhance-A-Video: the cross-frame attention boost of a self-attention output);
  *    icv_attention_fwd_radial (radial self-attention in one launch: every frame in reach, bands that halve with the distance);
- *    icv_l1_change_f64 and icv_easycache_predict_f32 (EasyCache: the sums of the skip rule and a skipped step's head outputs). */
+ *    icv_l1_change_f64 and icv_easycache_predict_f32 (EasyCache: the sums of the skip rule and a skipped step's head outputs);
+ *    icv_latent_resize_noise_f32 (coarse-to-fine sampling: the coarse x0-prediction resized and noised to the fine stage's first sigma). */
 #define ICV_ABI_VERSION 5
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -702,6 +703,25 @@ int icv_l1_change_f64(const float* a, int64_t lda, float* b, int64_t ldb, int64_
                       double* workspace, double* out2, void* stream);
 int icv_easycache_predict_f32(const float* x, const float* x_last, const float* hc_last, const float* hu_last, float* hc, float* hu,
                               int64_t ldh, int64_t C, int64_t T, int64_t H8, int64_t W8, int64_t tok0, int64_t n_tok, void* stream);
+
+/* ---- coarse-to-fine sampling: coarse_steps ------------------------------------------------------------------
+ * icv_latent_resize_noise_f32: the stage switch.  x0 f32 [planes, h_in, w_in] (the coarse stage's x0-prediction, read only),
+ * noise_out f32 [planes, h_out, w_out] (on entry the fine stage's noise, on return its start latent), both contiguous:
+ *   noise_out[p, Y, X] <- (1 - sigma) * up(x0)[p, Y, X] + sigma * noise_out[p, Y, X]
+ * up is the bilinear resize of every plane with half-pixel centres.  Per output element, every operation one f32 rounding and no
+ * fused multiply-add, with scale_y = (float)h_in / (float)h_out divided in f32:
+ *   sy = max((Y + 0.5) * scale_y - 0.5, 0);  y0 = min(floor(sy), h_in - 1);  y1 = min(y0 + 1, h_in - 1);  ly = sy - y0
+ *   (the same in x: scale_x, sx, x0, x1, lx);  a, b = x0[p, y0, x0], x0[p, y0, x1];  c, d = x0[p, y1, x0], x0[p, y1, x1]
+ *   v = (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d)
+ * and the output is icv_add_noise_f32's arithmetic on (v, noise): 1 - sigma formed in f32, two products, one sum; round_bf16 != 0
+ * rounds both products and the sum to bf16 (v itself is not rounded).  With h_out == h_in and w_out == w_in, ly = lx = 0 exactly
+ * and the result is icv_add_noise_f32's bit for bit.  h_out >= h_in >= 1 and w_out >= w_in >= 1 (an error otherwise: this is not
+ * a downsampler); any 4-byte-aligned pointers (16-byte accesses over noise_out's flat run of elements from its first 16-byte
+ * boundary on, element by element before and after); x0 must not overlap noise_out.  Only noise_out's planes * h_out * w_out
+ * elements are written.  planes == 0 launches nothing; a negative plane count, a null pointer, sizes out of order or more than
+ * 2^31 - 1 output elements are errors, checked on the host before the launch. */
+int icv_latent_resize_noise_f32(const float* x0, float* noise_out, int64_t planes, int64_t h_in, int64_t w_in, int64_t h_out,
+                                int64_t w_out, float sigma, int round_bf16, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ objs=()
 running=0
 max_jobs="${MAX_JOBS:-16}"       # concurrent hipcc processes: one per CPU this build may use, not one per source
 mkdir -p "$here/build"
-srcs=(api elementwise gemm gemm256 gemm256p gemm_fp8 fp8 attention attn2 attn7 attn7p attn7r attn8 buffers voxels vae_ops dit_forward comm ipc conv teacache sliding_window lora v2v multistep guidance inpaint nag enhance easycache)
+srcs=(api elementwise gemm gemm256 gemm256p gemm_fp8 fp8 attention attn2 attn7 attn7p attn7r attn8 buffers voxels vae_ops dit_forward comm ipc conv teacache sliding_window lora v2v multistep guidance inpaint nag enhance easycache coarse)
 tag=""
 if [[ "${ICV_EXPERIMENTS:-0}" == "1" ]]; then
   srcs+=(experiments/attn1 experiments/attn3 experiments/attn4 experiments/attn5 experiments/attn6 experiments/attn9 experiments/attn7q experiments/gemm256w experiments/gemm256x)

@@ -126,6 +126,7 @@ SIGNATURES.update({
     "icv_enhance_apply_bf16": (c_int, [_P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _P]),
     "icv_l1_change_f64": (c_int, [_P, _I, _P, _I, _I, _I, c_int, _P, _P, _P]),
     "icv_easycache_predict_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "icv_latent_resize_noise_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _F, c_int, _P]),
 })
 
 class KVPiece(ctypes.Structure):

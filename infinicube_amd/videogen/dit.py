@@ -195,6 +195,9 @@ class WanDiT:
         # set by prepare(); here so that everything else reads them as plain attributes
         self.kv_gather, self.kv8, self.fp8_wire, self.attn_arrival, self.sp_err = None, None, False, False, None
         self._native, self._pair, self._twin = None, None, None
+        # coarse-to-fine sampling (coarse.py): the twins prepared for a coarse grid, by (height, width, num_frames); they outlive
+        # prepare(), so that a second call of the same sizes rebuilds nothing
+        self._coarse_engines = {}
         # LoRA adapters merged into the matrices above (apply_lora): [(adapter id, alpha)] in merge order, and which
         # (weight name, layer) they touched - what restore_lora re-uploads
         self.lora_applied, self.lora_touched = [], set()
@@ -1073,6 +1076,7 @@ class WanDiT:
         t._nag, t._nag_buf = None, None
         t._enhance, t._enhance_slot, t._enhance_ws, t._enhance_E, t.enhance_scores = None, 0, None, None, None
         t._easy_state = None
+        t._coarse_engines = {}
         return t
 
     def _pair_engine(self):
@@ -1456,6 +1460,32 @@ class WanDiT:
             eng.prepare(TokenGrid(4 * (frames - 1) + 1, self.grid.height, self.grid.width), graphs=self._graphs_on)
             self._win_engines[frames] = eng
         eng.cfg_batch, eng.share_stem, eng.native_forward = self.cfg_batch, self.share_stem, self.native_forward
+        return eng
+
+    # Coarse-to-fine sampling (coarse.py): the first steps of a call run on a twin prepared for a smaller frame size;
+    # the caller drives two denoise() calls, one on the twin and one on this engine, with ops.latent_resize_noise between them.
+    def coarse_engine(self, height: int, width: int):
+        """The engine of a call's coarse stage: a twin on the same weights (text K/V caches are shared by reference) with a workspace
+        of its own for ``TokenGrid(num_frames, height, width)``, the frames of the grid this engine is prepared for.  Kept between
+        calls, one per (height, width, num_frames); it takes this engine's driver mode (CFG pair, shared stem, dual stream, hipGraph,
+        the C driver) and attention window.  One rank only: sequence / CFG-branch parallelism raises."""
+        if self.plan is None:
+            raise ValueError("coarse_engine: prepare() this engine for the call's grid first")
+        if self.sp_on or self.plan.world > 1:
+            raise ValueError("coarse_engine: coarse-to-fine sampling (coarse_steps) cannot be combined with sequence / CFG-branch "
+                             "parallelism (world > 1) yet")
+        grid = TokenGrid(self.grid.num_frames, height, width)
+        if grid.S >= self.grid.S or height > self.grid.height or width > self.grid.width:
+            raise ValueError(f"coarse_engine: {height}x{width} is not a coarser grid than the prepared {self.grid.height}x{self.grid.width}")
+        key = (height, width, grid.num_frames)
+        eng = self._coarse_engines.get(key)
+        if eng is None:
+            eng = self._engine_copy()
+            eng.prepare(grid, graphs=self._graphs_on)
+            self._coarse_engines[key] = eng
+        eng.cfg_batch, eng.share_stem, eng.native_forward = self.cfg_batch, self.share_stem, self.native_forward
+        eng.dual_stream, eng._graphs_on = self.dual_stream, self._graphs_on
+        eng.attn_window, eng.attn_radial = self.attn_window, self.attn_radial
         return eng
 
     def _denoise_windows(self, latent, ctxs, buf_tokens, scheduler, cfg_scale, steps, on_step, round_bf16, sw, known=None):

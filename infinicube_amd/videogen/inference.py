@@ -171,6 +171,10 @@ class WanVideoGenerator:
             from . import enhance
             if enhance.validate(getattr(self.pipe, "enhance_weight", None)) is not None:
                 raise ValueError("pipe.enhance_weight cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
+            from . import coarse
+            if coarse.validate(getattr(self.pipe, "coarse_steps", None), getattr(self.pipe, "coarse_size", None),
+                               self.pipe.num_inference_steps, height, width) is not None:
+                raise ValueError("pipe.coarse_steps cannot be combined with ICV_WORLD > 1 (more than one rank) yet")
             if seed is None:           # unseeded call: ONE drawn seed for every rank (each would otherwise draw its own noise)
                 seed = int.from_bytes(os.urandom(7), "little")
             frames = self._pool.generate(semantic_buffer, coordinate_buffer,

@@ -606,6 +606,23 @@ class HipOps:
         native.check(self.lib.icv_add_noise_f32(x0.data_ptr(), noise.data_ptr(), out.data_ptr(), out.numel(), float(sigma),
                                                 int(bool(round_bf16)), self._stream()), "icv_add_noise_f32")
 
+    # ---- coarse-to-fine sampling (coarse.py) -------------------------------------------
+    def latent_resize_noise(self, x0, noise_out, sigma: float, round_bf16=False):
+        """noise_out <- (1 - sigma) * up(x0) + sigma * noise_out in ONE launch (icv_latent_resize_noise_f32): x0 f32 [..., h_in, w_in],
+        noise_out f32 [..., h_out, w_out] with the same leading dimensions, h_out >= h_in and w_out >= w_in; up is the bilinear
+        resize of every plane with half-pixel centres, no fused multiply-add; with round_bf16 the two products and the sum of the
+        noising are rounded to bf16.  x0 is read only and must not overlap noise_out."""
+        _chk(x0, F32, "latent_resize_noise.x0"); _chk(noise_out, F32, "latent_resize_noise.noise_out")
+        if x0.dim() < 2 or x0.dim() != noise_out.dim() or tuple(x0.shape[:-2]) != tuple(noise_out.shape[:-2]):
+            raise ValueError(f"latent_resize_noise: x0 {tuple(x0.shape)} and noise_out {tuple(noise_out.shape)} must be [..., h, w] with the same leading dimensions")
+        (h_in, w_in), (h_out, w_out) = x0.shape[-2:], noise_out.shape[-2:]
+        if h_out < h_in or w_out < w_in:
+            raise ValueError(f"latent_resize_noise: the output plane {(h_out, w_out)} must be at least the input plane {(h_in, w_in)} in both dimensions")
+        assert x0.is_contiguous() and noise_out.is_contiguous()
+        planes = noise_out.numel() // max(h_out * w_out, 1)
+        native.check(self.lib.icv_latent_resize_noise_f32(x0.data_ptr(), noise_out.data_ptr(), planes, h_in, w_in, h_out, w_out, float(sigma),
+                                                          int(bool(round_bf16)), self._stream()), "icv_latent_resize_noise_f32")
+
     # ---- regenerating part of a clip (inpaint.py, DESIGN.md §16) -------------------------------------
     def latent_keep_mask(self, mask_u8, keep_u8):
         """mask u8 [N, H, W] (non-zero = regenerate) -> keep u8 [(N - 1) / 4 + 1, H / 8, W / 8]: 1 where every mask byte of the

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import attn_window, easycache, enhance, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
+from . import attn_window, coarse, easycache, enhance, guidance, inpaint, lora, multigpu, nag, options, sliding_window, solver, teacache, v2v
 from .config import TokenGrid, WanDiTConfig, infer_config_from_state_dict
 from .io import load_sharded_state_dict
 from .scheduler import FlowMatchScheduler
@@ -287,6 +287,12 @@ class WanVideoPipeline:
         # True turns attention_window_frames / attention_sink_frames into the dense run and the anchor of a radial mask.  The call's
         # attention_window_record then carries "radial": True, "key_fraction" in rows and "max_pieces"
         self.attention_radial = None
+        # Coarse-to-fine sampling (coarse.py): attributes behind the keywords of the same names, no environment route; the
+        # first coarse_steps steps run at coarse_size (None: half of each dimension, rounded down to a multiple of 16) on a twin engine,
+        # one launch resizes and re-noises the x0-prediction, the remaining steps run at the call's size.  coarse_record: {"steps", "size",
+        # "sigma", "tokens"} of the last call
+        self.coarse_steps = self.coarse_size = None
+        self.coarse_record = None
         # ICV_REFERENCE_ROUNDING=1 / pipe.reference_rounding = True: reproduce the rounding points of a pipeline that keeps
         # timestep, noise, noise_pred and latents in torch_dtype=bf16 ([EXT] upstream DiffSynth; ORACLE_RISKS.md R1-R3).
         # Default False: exact float timestep, fp32 noise / latents / CFG / Euler (more accurate; not what a bf16
@@ -476,7 +482,7 @@ class WanVideoPipeline:
                  cfg_zero_init_steps: Optional[int] = None, input_mask=None, nag_scale: Optional[float] = None,
                  nag_tau: Optional[float] = None, nag_alpha: Optional[float] = None, enhance_weight: Optional[float] = None,
                  attention_radial: Optional[bool] = None, easy_cache_thresh: Optional[float] = None,
-                 easy_cache_warmup_steps: Optional[int] = None, **unused):
+                 easy_cache_warmup_steps: Optional[int] = None, coarse_steps: Optional[int] = None, coarse_size=None, **unused):
         if self.text_encoder is None or self.vae is None:
             raise RuntimeError("WanVideoPipeline: text encoder / VAE not loaded")
         opt = options.resolve(self, dict(locals(), tea_cache_model_id=tea_cache_model_id or None))     # keyword, else attribute
@@ -491,6 +497,7 @@ class WanVideoPipeline:
         self.nag_record = None                       # ... and so are nag_scale / nag_tau / nag_alpha (keyword, else attribute)
         self.enhance_record = None                   # ... and enhance_weight
         self.easy_cache_record = None                # ... and easy_cache_thresh / easy_cache_warmup_steps
+        self.coarse_record = None                    # ... and coarse_steps / coarse_size
         # every setting, then the scope of their combination, is checked here, before any GPU work (the engine packs the weights
         # into HBM).  Sliding windows count when the plan has more than one (the clip fits one window: today's path, same launches,
         # same bits), the attention window when it does not cover the clip (the same).
@@ -515,6 +522,8 @@ class WanVideoPipeline:
         enhance_on = enhance.validate(self.enhance_weight if enhance_weight is None else enhance_weight)      # weight | None
         easy_on = easycache.validate(self.easy_cache_thresh if easy_cache_thresh is None else easy_cache_thresh,
                                      self.easy_cache_warmup_steps if easy_cache_warmup_steps is None else easy_cache_warmup_steps)
+        coarse_on = coarse.validate(self.coarse_steps if coarse_steps is None else coarse_steps,
+                                    self.coarse_size if coarse_size is None else coarse_size, num_inference_steps, height, width)
         world, rank = 1, 0
         try:
             import torch.distributed as dist
@@ -542,6 +551,9 @@ class WanVideoPipeline:
             enhance.check_call(world, windows, grid.T)
         if easy_on is not None:
             easycache.check_call(world, windows, opt.tea_cache_l1_thresh is not None)
+        if coarse_on is not None:
+            coarse.check_call(coarse_on[0], world, windows, opt.tea_cache_l1_thresh is not None, easy_on is not None,
+                              v2v_frames is not None, input_mask is not None, first_step)
         engine = self._get_engine()
         ops = engine.ops
         tc_thresh, tc_id = teacache.settings(opt.tea_cache_l1_thresh, opt.tea_cache_model_id, engine.cfg,
@@ -576,6 +588,13 @@ class WanVideoPipeline:
             self.attention_window_record = (attn_window.radial_record(grid.T, grid.tokens_per_frame, *aw) if radial
                                             else attn_window.record(grid.T, *aw))
         self.scheduler = FlowMatchScheduler(num_inference_steps, sigma_shift, self.reference_rounding, denoising_strength=strength)
+        # coarse-to-fine: the twin engine of the coarse grid (kept between calls) and the scheduler of its K steps, over
+        # the first K sigmas of the call's own list - its last step goes to 0, so the coarse latent ends as the x0-prediction
+        lo = lo_grid = lo_scheduler = None
+        if coarse_on is not None:
+            lo_grid = TokenGrid(num_frames, *coarse_on[1])
+            lo = engine.coarse_engine(*coarse_on[1])
+            lo_scheduler = FlowMatchScheduler.from_sigmas(self.scheduler.sigmas[:coarse_on[0]], self.reference_rounding)
         # i2v (BASELINE.json config #5): CLIP tokens + conditioning latent of the first frame, once per call
         i2v = engine.cfg.has_image_input
         clip_fea = None
@@ -609,6 +628,12 @@ class WanVideoPipeline:
                 dist.broadcast_object_list(box, src=0)
                 seed = int(box[0])
         g.manual_seed(int(seed))
+        latent_lo = None
+        if lo is not None:                            # the FIRST draw of the call's generator is the coarse stage's noise
+            latent_lo = torch.randn((1, 16) + lo_grid.latent_shape()[1:], generator=g, dtype=torch.float32)[0]
+            if self.reference_rounding:
+                latent_lo = latent_lo.to(torch.bfloat16).to(torch.float32)
+            latent_lo = ops.to_device(latent_lo, torch.float32)
         latent = torch.randn((1, 16) + grid.latent_shape()[1:], generator=g, dtype=torch.float32)[0]
         if self.reference_rounding:
             latent = latent.to(torch.bfloat16).to(torch.float32)
@@ -627,14 +652,19 @@ class WanVideoPipeline:
         n_buf, known = len(vids), None
         if v2v_frames is not None:                    # the input clip rides in the buffers' pass (alone when there are none)
             vids = vids + (v2v_frames,)
-        if vids:
+
+        def encode_clips(h, w):
             if hasattr(self.vae, "encode_many"):      # the clips in one pass over their tiles, bytes normalised on the device
                 to_clip = _video_to_uint8 if getattr(self.vae, "accepts_uint8", False) else _video_to_tensor
-                lats = self.vae.encode_many([to_clip(v, height, width) for v in vids], tiled=tiled, tile_size=tile_size,
+                return self.vae.encode_many([to_clip(v, h, w) for v in vids], tiled=tiled, tile_size=tile_size,
                                             tile_stride=tile_stride, **vshard)
-            else:
-                lats = [self.vae.encode(_video_to_tensor(v, height, width), tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
-                        for v in vids]
+            return [self.vae.encode(_video_to_tensor(v, h, w), tiled=tiled, tile_size=tile_size, tile_stride=tile_stride) for v in vids]
+
+        if vids:
+            lats = encode_clips(height, width)
+        buf_tokens_lo = None
+        if n_buf and lo is not None:                  # the coarse stage's buffers: the same clips resized to its size, encoded, embedded
+            buf_tokens_lo = lo.embed_buffers(torch.cat([x.to(torch.float32) for x in encode_clips(lo_grid.height, lo_grid.width)], dim=0))
         if n_buf:
             # sliding windows: the buffers were VAE-encoded for the whole clip ONCE; their tokens too, a window reads a row range
             buf_tokens = engine.embed_buffers(torch.cat([x.to(torch.float32) for x in lats[:n_buf]], dim=0),
@@ -664,6 +694,9 @@ class WanVideoPipeline:
         if i2v:
             y = self._image_cond_latents(input_image, grid, tiled, tile_size, tile_stride)
             buf_tokens = engine.embed_cond_latents(y, add_to=buf_tokens)
+            if lo is not None:                        # ... and the first-frame conditioning once more, on the coarse grid
+                buf_tokens_lo = lo.embed_cond_latents(self._image_cond_latents(input_image, lo_grid, tiled, tile_size, tile_stride),
+                                                      add_to=buf_tokens_lo)
         if tune_key is not None and tune_key not in self._kv_tuned:
             self._kv_tuned[tune_key] = self._autotune_kv(engine, latent, ctx_c if ctx_c is not None else ctx_u, buf_tokens, ops)
         # TeaCache: the skip schedule of the whole call, decided on rank 0 and broadcast (every rank must skip the same steps, or the
@@ -681,10 +714,29 @@ class WanVideoPipeline:
         if solver_name is not None:
             solver_plan = solver.MultistepPlan(solver_name, self.scheduler.sigmas)
             self.solver_record = solver_plan.record(range(first_step, num_inference_steps))
+            if lo is not None:                        # one plan per stage; the history starts anew at step K: the orders of both, in step order
+                solver_lo = solver.MultistepPlan(solver_name, lo_scheduler.sigmas)
+                orders = (solver_lo.record(range(first_step, coarse_on[0]))["orders"]
+                          + solver_plan.record(range(coarse_on[0], num_inference_steps))["orders"])
+                self.solver_record = dict(self.solver_record, steps=len(orders), orders=orders)
         # the hot loop (HIP)
         it = range(num_inference_steps)
         if progress_bar_cmd is not None:
             it = progress_bar_cmd(it)
+        scales_lo = []
+        if lo is not None:
+            # coarse stage: steps 0 .. K-1 on the twin, then ONE launch turns its x0-prediction into the fine stage's start latent
+            # x_K = (1 - sigma_K) up(x0) + sigma_K noise, in the fine noise's own tensor; the fine stage consumes the rest of ``it``
+            import itertools
+            it = iter(it)
+            lo.denoise(latent_lo, ctx_c, ctx_u, buf_tokens_lo, lo_scheduler, cfg_scale, steps=itertools.islice(it, coarse_on[0]),
+                       round_bf16=self.reference_rounding, solver=solver_lo if solver_plan is not None else None, guidance=gd_plan,
+                       **(dict(nag=nag_plan) if nag_plan is not None else {}),
+                       **(dict(enhance=enhance_plan) if enhance_plan is not None else {}))
+            scales_lo = lo.guidance_scales or []
+            sigma_k = self.scheduler.sigmas[coarse_on[0]]
+            ops.latent_resize_noise(latent_lo, latent, sigma_k, round_bf16=self.reference_rounding)
+            self.coarse_record = coarse.record(coarse_on[0], coarse_on[1], sigma_k, (lo_grid.S, grid.S))
         engine.denoise(latent, ctx_c, ctx_u, buf_tokens, self.scheduler, cfg_scale, steps=it,
                        branch_exchange=BranchExchange(layout) if layout.mode == "cfg+sp" else None,
                        round_bf16=self.reference_rounding, tea_cache=tc_plan, sliding_window=sw_plan, solver=solver_plan, guidance=gd_plan,
@@ -696,7 +748,7 @@ class WanVideoPipeline:
         if enhance_plan is not None:
             self.enhance_record = enhance_plan.record(engine.grid.T, engine.enhance_scores)
         if gd_plan is not None:
-            self.guidance_record = gd_plan.record(engine.guidance_scales)
+            self.guidance_record = gd_plan.record(scales_lo + (engine.guidance_scales or []))
         latent = gather_latent(latent, plan, grid, group=layout.sp_group)
         # The DECODE is sharded (a collective of every rank: vae.TileShard broadcasts the tiles) only where every rank is known to
         # take part: behind a multigpu.WorkerPool (its workers pass join_decode=True) or when the caller says so

@@ -50,6 +50,21 @@ class FlowMatchScheduler:
         if self.reference_rounding:
             self.timesteps = [round_through_bf16(t) for t in self.timesteps]
 
+    @classmethod
+    def from_sigmas(cls, sigmas, reference_rounding: bool = False) -> "FlowMatchScheduler":
+        """A scheduler over an explicit sigma list, e.g. the first K sigmas of a call (coarse-to-fine sampling): the
+        floats are kept as they are, the timesteps get the same ``reference_rounding``, and the last step goes to 0 as always."""
+        sch = cls.__new__(cls)
+        sch.reference_rounding = reference_rounding
+        sch.denoising_strength = None                     # not a range this class built
+        sch.sigmas = [float(s) for s in sigmas]
+        if not sch.sigmas:
+            raise ValueError("FlowMatchScheduler.from_sigmas: an empty sigma list")
+        sch.timesteps = [s * 1000.0 for s in sch.sigmas]
+        if reference_rounding:
+            sch.timesteps = [round_through_bf16(t) for t in sch.timesteps]
+        return sch
+
     def dsigma(self, i: int) -> float:
         """sigma_{i+1} - sigma_i with sigma_N = 0 (the Euler step multiplier)."""
         nxt = self.sigmas[i + 1] if i + 1 < len(self.sigmas) else 0.0
